@@ -63,7 +63,48 @@ def parse():
                     help="N>1: small exchanges of the hub rows per epoch (ge_sync_epoch); 0 = the library's choice (by the busiest column; at least max(8, ranks)), -1 = none (one exchange per epoch for every row)")
     ap.add_argument("--no-other-form", action="store_true", help="N>1: do not time the other exchange form behind the quoted region")
     ap.add_argument("--accum-sync-every", type=int, default=4, help="every how many context syncs the AdaGrad accumulators are reconciled too (N>1)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="rank 0, after the result line: replay the timed path reproducibly (one worker, a seeded sample of the nonzeros, "
+                         "REPLAY_EPOCHS epochs; a few seconds) and write what the replay computed to DIR/replay_<name>.npy, under 64 MB")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
+
+
+DUMP_SEED = 0x5EED
+REPLAY_NONZEROS = 1 << 20
+REPLAY_EPOCHS = 3
+
+
+def dump_outputs(path, cfg, opt, V, I, J, X, xmax):
+    """--dump-outputs: what the timed path computes, in a form two builds can compare output for output.  The timed handle itself cannot
+    give that: thousands of Hogwild workers race on shared context rows, which update a race loses depends on timing, and two runs on the
+    same inputs end in different tables (the step costs of the timed run are in the result line).  So the timed path is REPLAYED: a second
+    handle with the timed handle's configuration, kernel, chunking and device shuffle, hub columns by its rule (its count threshold as a
+    share of the nonzeros), but ONE worker -- the kernel as a sequential program, the same bits every run -- on a fixed, seeded sample of
+    REPLAY_NONZEROS of the same nonzeros, for REPLAY_EPOCHS epochs (iterations 0, 1, ...; one worker takes 0.7 - 0.9 us per update, so
+    about a second per epoch).  What only many workers do (concurrent hub flushes, the N > 1 exchange) is not in the replay.
+    replay_epoch_cost.npy = the summed job cost of each replayed epoch (float64); replay_<table>.npy = the same seeded sample of rows from
+    every state table of the same length after the last replayed epoch (focus rows and their biases and accumulators match row for row),
+    float32."""
+    import geglove
+    from geglove import capi
+    os.makedirs(path, exist_ok=True)
+    n = int(I.shape[0])
+    sel = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(REPLAY_NONZEROS, n), replace=False))
+    rep = geglove.createOptimizer(cfg, geglove.CooMatrix(V, I[sel], J[sel], X[sel], xmax), workers=1, hot_theta=opt.info()["hot_threshold"] / n)
+    costs = [rep.epoch(it) for it in range(REPLAY_EPOCHS)]
+    np.save(os.path.join(path, "replay_epoch_cost.npy"), np.asarray(costs, np.float64))
+    names = capi.STATE_NAMES if rep.OPT == capi.GE_OPT_ADAGRAD else capi.ALL_STATE_NAMES
+    per_table = min(8192, (60 << 20) // (4 * len(names) * (rep.dimension + 1)))     # rows per table: the whole dump under 64 MB
+    for name in names:
+        a = rep.get_state(name)
+        if not name.endswith("bias"):
+            a = a.reshape(-1, rep.dimension)
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(a.shape[0], size=min(per_table, a.shape[0]), replace=False))
+        np.save(os.path.join(path, "replay_" + name + ".npy"), np.ascontiguousarray(a[pick], np.float32))
+    rep.close()
 
 
 def cpu_model():
@@ -384,6 +425,8 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, V, D, I, J, X, xmax)
         print(json.dumps(out), flush=True)
+        if args.dump_outputs:                 # behind the result line and every timed or exchanged step of every rank
+            dump_outputs(args.dump_outputs, cfg, opt, V, I, J, X, xmax)
     if sync is not None:
         sync.close()                  # the RCCL communicator goes before the handle it serves
     opt.close()

@@ -138,15 +138,16 @@ def test_configuration_check_messages(host, tmp_path):
         geglove.Configuration.check(geglove.Configuration({"graph": "g"}))
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/dblp.config.yml"), reason="reference tree not present on this box")
 def test_shipped_reference_yamls_load(host):
+    """The reference's three shipped configurations, stored verbatim under tests/golden/."""
     names = {"dblp": "dblp-2015-2017_pglove_partial_directed_0.1_0.001_adagrad_pca_300",
              "onstage": "onstage_pglove_partial_directed_0.1_0.001_adagrad_pca_300",
              "saa": "saa_pglove_partial_directed_0.1_0.001_adagrad_pca_300"}
     for n, fname in names.items():
-        out = host.geh_config_summary(("/root/reference/%s.config.yml" % n).encode(), 1).decode().splitlines()
+        path = os.path.join(GOLD, "%s.config.yml" % n)
+        out = host.geh_config_summary(path.encode(), 1).decode().splitlines()
         assert out[0] == "OK" and ("name=" + fname) in out
-        py = geglove.Configuration.load("/root/reference/%s.config.yml" % n)
+        py = geglove.Configuration.load(path)
         geglove.Configuration.check(py)
         assert py.getDim() == 300 and py.getMethod() == "pglove" and py.getAlpha() == 0.1 and py.isDirected()
 

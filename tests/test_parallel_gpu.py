@@ -526,13 +526,17 @@ def test_two_ranks_live_exchange_beside_a_running_epoch(gpu):
     epoch BESIDE the epoch kernel -- take, host sum, atomic land on a stream of their own while the kernel's workers publish their own
     deltas into the same rows.  The run must stay live (its exchanges keep the epoch's pace), end in identical replicas and follow a
     single-handle run of the same library on the whole matrix (same seed; the sharded run's order differs, so: a band).  In a process of
-    its own: whether an exchange is late is a matter of host timing, and a test process that has run hundreds of GPU tests is no measure."""
+    its own: whether an exchange is late is a matter of host timing, and a test process that has run hundreds of GPU tests is no measure.
+    That process holds five streams (each rank's handle stream and exchange stream, and the null stream), one more than the runtime's default
+    of four hardware queues: the fifth then shares a queue (which one varies from run to run, so at four the test failed only now and then),
+    and an exchange stream that shares one with an epoch stream waits for the whole epoch kernel before it can even read the ticket counter.  GPU_MAX_HW_QUEUES=8 gives every stream a queue of its own, as two one-rank
+    processes have."""
     import json
     import subprocess
     import sys
     here = os.path.dirname(os.path.abspath(__file__))
     r = subprocess.run([sys.executable, "-c", "import conftest, test_parallel_gpu as T; T._live_scenario()"], cwd=here, capture_output=True, text=True, timeout=360,
-                       env=dict(os.environ, GE_SYNC_DEBUG="1", GE_LOCAL_GROUP_TIMEOUT_S="120"))
+                       env=dict(os.environ, GE_SYNC_DEBUG="1", GE_LOCAL_GROUP_TIMEOUT_S="120", GPU_MAX_HW_QUEUES="8"))
     line = [l for l in r.stdout.splitlines() if l.startswith("LIVE ")]
     assert r.returncode == 0 and line, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
     d = json.loads(line[-1][5:])

@@ -1,4 +1,4 @@
-import sys; sys.path[:0]=['/root/repo/graph-embeddings_amd','/root/repo/oracle','/root/repo/tests']
+import os, sys; _R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path[:0]=[os.path.join(_R, 'graph-embeddings_amd'), os.path.join(_R, 'oracle'), os.path.join(_R, 'tests')]
 import numpy as np, geglove, oracle as O
 from geglove import synth
 from helpers import make_config, OPT_KIND

@@ -16,8 +16,8 @@
 //   land:  c += wire (mean rule: wire / count);  table = c + (table - c_old - own)
 // (bf16 rows go through ge_exchange_turn_bf16, whose base is consensus + own in flight.)
 // The table itself is never on the wire, so the epoch kernel may keep updating it while the all-reduce runs.
-// Transport: RCCL over xGMI (loaded at run time, so a single-GPU user needs no RCCL), or three callbacks of the host
-// (tests run two ranks on one GPU over gloo; the C++ CLI rehearses N ranks inside one process).
+// Transport: one implementation of Collective (below), picked by ge_sync_create: RCCL over xGMI (loaded at run time, so a single-GPU user
+// needs no RCCL), a local group (the C++ CLI rehearses N ranks inside one process) or three callbacks of the host (tests: gloo).
 // The wire / base buffers are DENSE [rows x cols] whatever the table's row stride (fat rows, interleaved records).
 #include "ge_common.h"
 
@@ -28,6 +28,7 @@
 #include <condition_variable>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <chrono>
@@ -46,9 +47,9 @@ const std::vector<int32_t> *glove_kernel_hubs(const ge_glove *h);
 
 namespace {
 
-__device__ __forceinline__ float bf16_to_f32(uint32_t h) { return __uint_as_float(h << 16); }
-__device__ __forceinline__ uint32_t f32_to_bf16_rne(float f) {
-    uint32_t u = __float_as_uint(f);
+__host__ __device__ __forceinline__ float bf16_to_f32(uint32_t h) { return __builtin_bit_cast(float, h << 16); }     // (host: the local group's sums)
+__host__ __device__ __forceinline__ uint32_t f32_to_bf16_rne(float f) {
+    uint32_t u = __builtin_bit_cast(uint32_t, f);
     if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;       // NaN stays NaN
     return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
 }
@@ -100,31 +101,19 @@ __global__ __launch_bounds__(256) void k_sync_turn(float *__restrict__ table, in
 // on base / wire / own covers one contiguous kilobyte (512 bytes on a bf16 buffer) whatever the row length, and all 64 lanes work
 // (a wave per row left 14 of 64 lanes idle at dim 200 and read the dense buffers in 800-byte pieces n_waves rows apart).  The
 // table side follows the records: group q lives in row q / cols4.  U groups per thread are loaded before any is stored.
-// NT: the dense buffers are touched once per exchange and never fit a cache -- nontemporal accesses keep them out of the way of
-// the table's lines.
-template <bool LAND, bool TAKE, bool W16, bool NT>
+// The dense buffers are touched once per exchange and never fit a cache: nontemporal accesses keep them out of the way of the
+// table's lines.
+template <bool LAND, bool TAKE, bool W16>
 __global__ __launch_bounds__(256) void k_sync_turn_flat4(float *__restrict__ table, int64_t t_stride, uint32_t cols4, uint32_t n4,
                                                          float *__restrict__ base, void *__restrict__ wire_, void *__restrict__ own_) {
     constexpr int U = 4;
     const uint32_t step = gridDim.x * blockDim.x;
     typedef float v4f __attribute__((ext_vector_type(4)));
     typedef unsigned v2u __attribute__((ext_vector_type(2)));
-    auto ld4 = [](const float4 *p) -> float4 {
-        if constexpr (NT) { const v4f v = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(p)); return make_float4(v.x, v.y, v.z, v.w); }
-        else return *p;
-    };
-    auto ld2 = [](const uint2 *p) -> uint2 {
-        if constexpr (NT) { const v2u v = __builtin_nontemporal_load(reinterpret_cast<const v2u *>(p)); return make_uint2(v.x, v.y); }
-        else return *p;
-    };
-    auto st4 = [](float4 *p, float4 v) {
-        if constexpr (NT) { v4f w; w.x = v.x; w.y = v.y; w.z = v.z; w.w = v.w; __builtin_nontemporal_store(w, reinterpret_cast<v4f *>(p)); }
-        else *p = v;
-    };
-    auto st2 = [](uint2 *p, uint2 v) {
-        if constexpr (NT) { v2u w; w.x = v.x; w.y = v.y; __builtin_nontemporal_store(w, reinterpret_cast<v2u *>(p)); }
-        else *p = v;
-    };
+    auto ld4 = [](const float4 *p) -> float4 { const v4f v = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(p)); return make_float4(v.x, v.y, v.z, v.w); };
+    auto ld2 = [](const uint2 *p) -> uint2 { const v2u v = __builtin_nontemporal_load(reinterpret_cast<const v2u *>(p)); return make_uint2(v.x, v.y); };
+    auto st4 = [](float4 *p, float4 v) { v4f w; w.x = v.x; w.y = v.y; w.z = v.z; w.w = v.w; __builtin_nontemporal_store(w, reinterpret_cast<v4f *>(p)); };
+    auto st2 = [](uint2 *p, uint2 v) { v2u w; w.x = v.x; w.y = v.y; __builtin_nontemporal_store(w, reinterpret_cast<v2u *>(p)); };
     for (uint32_t q0 = blockIdx.x * blockDim.x + threadIdx.x; q0 < n4; q0 += U * step) {      // n4 < 2^29: vocab * dim < 2^31 (geglove.h)
         float4 tv[U], cv[U], wf[U], of[U]; uint2 wh[U], oh[U]; float4 *tp[U]; bool live[U];
 #pragma unroll
@@ -372,6 +361,22 @@ struct Entry {
 
 unsigned grid_for(int64_t n, int cus) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, (int64_t)cus * 8)); }
 
+// How the ranks' buffers meet: RCCL, a local group (rank threads of this process) or the host's callbacks (ge_transport).
+// ge_sync_create picks one; every collective of ge_sync goes through it.
+struct Collective {
+    hipStream_t main;                                                   // the handle's stream
+    explicit Collective(hipStream_t m) : main(m) {}
+    virtual ~Collective() = default;
+    virtual ge_status start(const std::vector<Entry *> &taken) = 0;    // the large exchange of entries just taken on main: own summed into wire (+ cnt in place) ...
+    virtual ge_status wait(std::vector<Entry> &ent) = 0;               // ... whose sums main's next work (the land) sees
+    virtual ge_status sum_small(float *d, int64_t n) = 0;              // fp32, in place: after main's work, before main's next
+    virtual ge_status sum_live(float *d, int64_t n, hipStream_t hub_side) = 0;   // fp32, in place, on hub_side beside the epoch kernel
+    virtual bool can_run_live() const { return true; }
+    virtual ge_status broadcast(float *d, int64_t n, int32_t src) = 0; // every rank's d becomes rank src's; ordered as sum_small
+    virtual ge_status reduce_f64(double *v, int32_t n, bool max) = 0;  // sum (or max) of host values, blocking
+    virtual void abort() {}                                             // this rank failed inside a call: its peers must not wait for it
+};
+
 }  // namespace
 
 // N ranks inside ONE process (one host thread each), on any number of devices: buffers meet in host memory.  What the C++
@@ -399,16 +404,10 @@ struct ge_local_group {
 
 struct ge_sync {
     ge_glove *h = nullptr;
-    ge_local_group *loop = nullptr;
     ge_sync_cfg cfg{};
-    ge_transport tr{};              // callbacks (copied); tr.start == nullptr: RCCL
-    ncclComm_t comm = nullptr;
+    std::unique_ptr<Collective> coll;   // world > 1: the transport
     hipStream_t main = nullptr;     // the handle's stream: take / land kernels are ordered with its epochs
-    hipStream_t side = nullptr;     // RCCL's stream: the all-reduce runs beside the next epoch
-    hipEvent_t ev_taken = nullptr, ev_reduced = nullptr;
-    ncclComm_t hub_comm = nullptr;  // the hub rows' small all-reduces: a communicator and a stream of their own, so that they need not
-    hipStream_t hub_side = nullptr; // queue behind the large all-reduce that runs under the epoch (ncclCommSplit; else the same pair)
-    hipEvent_t ev_hub_a = nullptr, ev_hub_b = nullptr;
+    hipStream_t hub_side = nullptr; // the live exchange beside the epoch kernel (RCCL: also the small all-reduces of the hub rows)
     int device = 0, cus = 256;
     std::vector<Entry> ent;
     std::vector<void *> owned;
@@ -436,51 +435,181 @@ struct ge_sync {
 
 namespace {
 
-// sum of every rank's device buffer, in rank order, back into each rank's buffer (blocking; the caller's stream is idle)
-// st: the stream the device copies are ordered on (nullptr: plain blocking copies -- they wait for the null stream, i.e. for an epoch kernel
-// running there; the live exchange passes its own stream)
-ge_status local_allreduce(ge_local_group *g, int rank, void *buf, int64_t count, int32_t dtype, bool bcast, int src, hipStream_t st = nullptr) {
-    const size_t bytes = (size_t)count * (dtype == GE_DTYPE_BF16 ? 2 : dtype == 2 ? 8 : 4);       // dtype 2: host doubles (scalars)
-    // a rank whose copy fails still reaches the barriers (its peers would wait for ever otherwise) and aborts the group
-    static const char *gone = "ge_local_group: another rank of the group failed";
-    std::vector<unsigned char> &mine = g->stage[(size_t)rank];
-    mine.resize(bytes);
-    hipError_t he = hipSuccess;
-    if (dtype == 2) std::memcpy(mine.data(), buf, bytes);
-    else if (st) { he = hipMemcpyAsync(mine.data(), buf, bytes, hipMemcpyDeviceToHost, st); if (he == hipSuccess) he = hipStreamSynchronize(st); }
-    else he = hipMemcpy(mine.data(), buf, bytes, hipMemcpyDeviceToHost);
-    if (he != hipSuccess) { g->abort(); return ge::fail(GE_ERR_HIP, "local all-reduce: copy to the host failed: %s", hipGetErrorString(he)); }
-    if (!g->barrier()) return ge::fail(GE_ERR_STATE, "%s", gone);
-    std::vector<unsigned char> out(bytes);
-    if (bcast) std::memcpy(out.data(), g->stage[(size_t)src].data(), bytes);
-    else if (dtype == GE_DTYPE_F32) {
-        float *o = (float *)out.data();
-        for (int64_t k = 0; k < count; ++k) { float a = 0.0f; for (int r = 0; r < g->world; ++r) a += ((const float *)g->stage[(size_t)r].data())[k]; o[k] = a; }
-    } else if (dtype == GE_DTYPE_BF16) {
-        uint16_t *o = (uint16_t *)out.data();
-        for (int64_t k = 0; k < count; ++k) {
-            float a = 0.0f;
-            for (int r = 0; r < g->world; ++r) { const uint32_t hbits = ((const uint16_t *)g->stage[(size_t)r].data())[k]; float f; const uint32_t u = hbits << 16; std::memcpy(&f, &u, 4); a += f; }
-            uint32_t u; std::memcpy(&u, &a, 4);
-            o[k] = (uint16_t)(((u & 0x7fffffffu) > 0x7f800000u) ? ((u >> 16) | 0x40u) : ((u + 0x7fffu + ((u >> 16) & 1u)) >> 16));
-        }
-    } else {
-        double *o = (double *)out.data();
-        for (int64_t k = 0; k < count; ++k) {
-            double a = ((const double *)g->stage[0].data())[k];
-            for (int r = 1; r < g->world; ++r) { const double v = ((const double *)g->stage[(size_t)r].data())[k]; a = src == 1 ? std::max(a, v) : a + v; }   // src doubles as the op for scalars
-            o[k] = a;
-        }
-    }
-    if (!g->barrier()) return ge::fail(GE_ERR_STATE, "%s", gone);      // every rank has read the stage
-    if (dtype == 2) std::memcpy(buf, out.data(), bytes);
-    else if ((he = st ? hipMemcpyAsync(buf, out.data(), bytes, hipMemcpyHostToDevice, st) : hipMemcpy(buf, out.data(), bytes, hipMemcpyHostToDevice)) != hipSuccess
-             || (st && (he = hipStreamSynchronize(st)) != hipSuccess)) {
-        g->abort();
-        return ge::fail(GE_ERR_HIP, "local all-reduce: copy to the device failed: %s", hipGetErrorString(he));
-    }
+// the transports that sum in place, on the host's side, get the send buffer copied into the receive buffer first (RCCL: own -> wire)
+ge_status wire_from_own(hipStream_t main, const std::vector<Entry *> &taken) {
+    for (Entry *e : taken) GE_HIP(hipMemcpyAsync(e->wire, e->own, (size_t)e->n * (e->w16 ? 2 : 4), hipMemcpyDeviceToDevice, main));
+    GE_HIP(hipStreamSynchronize(main));
     return GE_OK;
 }
+
+// RCCL: the large exchange and the broadcast on `side`, beside main (the all-reduce runs under the next epoch); the hub rows' small
+// all-reduces on a communicator and a stream of their own, so that they need not queue behind it
+struct RcclCollective final : Collective {
+    ncclComm_t comm = nullptr, hub_comm = nullptr;     // hub_comm: ncclCommSplit of comm, or comm itself
+    hipStream_t side = nullptr, hub_side = nullptr;    // hub_side: made here, owned by the caller
+    hipEvent_t ev_taken = nullptr, ev_reduced = nullptr, ev_hub_a = nullptr, ev_hub_b = nullptr;
+    using Collective::Collective;
+    ge_status init(int32_t world, int32_t rank, const void *id128, hipStream_t *hub_side_out) {
+        if (!rccl().ok) return ge::fail(GE_ERR_HIP, "RCCL is not available (librccl.so.1 could not be loaded)");
+        GE_HIP(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
+        GE_HIP(hipEventCreateWithFlags(&ev_taken, hipEventDisableTiming)); GE_HIP(hipEventCreateWithFlags(&ev_reduced, hipEventDisableTiming));
+        ncclUniqueId id; std::memcpy(&id, id128, sizeof(id));
+        const ncclResult_t r = rccl().CommInitRank(&comm, world, id, rank);
+        if (r != ncclSuccess) { comm = nullptr; return ge::fail(GE_ERR_HIP, "ncclCommInitRank failed: %s", rccl().GetErrorString(r)); }
+        GE_HIP(hipStreamCreateWithFlags(hub_side_out, hipStreamNonBlocking)); hub_side = *hub_side_out;
+        GE_HIP(hipEventCreateWithFlags(&ev_hub_a, hipEventDisableTiming)); GE_HIP(hipEventCreateWithFlags(&ev_hub_b, hipEventDisableTiming));
+        // Every rank makes the same choice: the symbol is there or it is not, GE_SYNC_HUB_COMM=shared turns the split off everywhere;
+        // a split that fails is an error, not a silent fallback that would leave the ranks on different communicators.
+        hub_comm = comm;
+        const char *hc = std::getenv("GE_SYNC_HUB_COMM");
+        if (rccl().CommSplit && !(hc && std::strcmp(hc, "shared") == 0)) {
+            ncclComm_t c2 = nullptr;
+            const ncclResult_t r2 = rccl().CommSplit(comm, 0, rank, &c2, nullptr);
+            if (r2 != ncclSuccess || !c2) return ge::fail(GE_ERR_HIP, "ncclCommSplit failed: %s (GE_SYNC_HUB_COMM=shared uses one communicator)", rccl().GetErrorString(r2));
+            hub_comm = c2;
+        }
+        return GE_OK;
+    }
+    ~RcclCollective() override {
+        if (side) (void)hipStreamSynchronize(side);
+        if (hub_comm && hub_comm != comm) (void)rccl().CommDestroy(hub_comm);
+        if (comm) (void)rccl().CommDestroy(comm);
+        for (hipEvent_t ev : {ev_hub_a, ev_hub_b, ev_taken, ev_reduced}) if (ev) (void)hipEventDestroy(ev);
+        if (side) (void)hipStreamDestroy(side);
+    }
+    ge_status start(const std::vector<Entry *> &taken) override {
+        GE_HIP(hipEventRecord(ev_taken, main)); GE_HIP(hipStreamWaitEvent(side, ev_taken, 0));
+        for (Entry *e : taken) {
+            GE_NCCL(rccl().AllReduce(e->own, e->wire, (size_t)e->n, e->w16 ? ncclBfloat16 : ncclFloat32, ncclSum, comm, side));
+            if (e->mean) GE_NCCL(rccl().AllReduce(e->cnt, e->cnt, (size_t)e->n, ncclFloat32, ncclSum, comm, side));
+        }
+        GE_HIP(hipEventRecord(ev_reduced, side));
+        return GE_OK;
+    }
+    ge_status wait(std::vector<Entry> &) override { GE_HIP(hipStreamWaitEvent(main, ev_reduced, 0)); return GE_OK; }
+    ge_status sum_small(float *d, int64_t n) override {
+        GE_HIP(hipEventRecord(ev_hub_a, main)); GE_HIP(hipStreamWaitEvent(hub_side, ev_hub_a, 0));
+        GE_NCCL(rccl().AllReduce(d, d, (size_t)n, ncclFloat32, ncclSum, hub_comm, hub_side));
+        GE_HIP(hipEventRecord(ev_hub_b, hub_side)); GE_HIP(hipStreamWaitEvent(main, ev_hub_b, 0));
+        return GE_OK;
+    }
+    ge_status sum_live(float *d, int64_t n, hipStream_t st) override { GE_NCCL(rccl().AllReduce(d, d, (size_t)n, ncclFloat32, ncclSum, hub_comm, st)); return GE_OK; }
+    ge_status broadcast(float *d, int64_t n, int32_t src) override {
+        GE_HIP(hipEventRecord(ev_taken, main)); GE_HIP(hipStreamWaitEvent(side, ev_taken, 0));
+        GE_NCCL(rccl().Broadcast(d, d, (size_t)n, ncclFloat32, src, comm, side));
+        GE_HIP(hipEventRecord(ev_reduced, side)); GE_HIP(hipStreamWaitEvent(main, ev_reduced, 0));
+        return GE_OK;
+    }
+    ge_status reduce_f64(double *v, int32_t n, bool max) override {
+        double *d = nullptr;
+        GE_HIP(hipMalloc((void **)&d, sizeof(double) * (size_t)n));
+        const std::unique_ptr<double, decltype(&hipFree)> d_owner(d, hipFree);
+        GE_HIP(hipMemcpyAsync(d, v, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, side));
+        GE_NCCL(rccl().AllReduce(d, d, (size_t)n, ncclFloat64, max ? ncclMax : ncclSum, comm, side));
+        GE_HIP(hipMemcpyAsync(v, d, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, side));
+        GE_HIP(hipStreamSynchronize(side));
+        return GE_OK;
+    }
+};
+
+// A local group, blocking: every rank copies its buffer to its stage in host memory, the ranks meet, each folds all stages into the
+// result (fold(out, stage): stage(r) = rank r's values, taken in rank order) and copies it back.  buf: host memory (on_host) or device
+// memory whose copies are ordered on st (nullptr: plain blocking copies -- they wait for the null stream, i.e. for an epoch kernel running
+// there; the live exchange passes its own stream).  A rank whose copy fails still reaches the barriers and aborts the group.
+struct LocalCollective final : Collective {
+    ge_local_group *g; int rank;
+    LocalCollective(hipStream_t m, ge_local_group *group, int r) : Collective(m), g(group), rank(r) {}
+    template <typename T, typename Fold> ge_status run(T *buf, int64_t count, bool on_host, hipStream_t st, Fold fold) {
+        static const char *gone = "ge_local_group: another rank of the group failed";
+        const size_t bytes = sizeof(T) * (size_t)count;
+        std::vector<unsigned char> &mine = g->stage[(size_t)rank];
+        mine.resize(bytes);
+        hipError_t he = hipSuccess;
+        if (on_host) std::memcpy(mine.data(), buf, bytes);
+        else if (st) { he = hipMemcpyAsync(mine.data(), buf, bytes, hipMemcpyDeviceToHost, st); if (he == hipSuccess) he = hipStreamSynchronize(st); }
+        else he = hipMemcpy(mine.data(), buf, bytes, hipMemcpyDeviceToHost);
+        if (he != hipSuccess) { g->abort(); return ge::fail(GE_ERR_HIP, "local all-reduce: copy to the host failed: %s", hipGetErrorString(he)); }
+        if (!g->barrier()) return ge::fail(GE_ERR_STATE, "%s", gone);
+        std::vector<T> out((size_t)count);
+        fold(out.data(), [&](int r) { return (const T *)g->stage[(size_t)r].data(); });
+        if (!g->barrier()) return ge::fail(GE_ERR_STATE, "%s", gone);      // every rank has read the stage
+        if (on_host) std::memcpy(buf, out.data(), bytes);
+        else if ((he = st ? hipMemcpyAsync(buf, out.data(), bytes, hipMemcpyHostToDevice, st) : hipMemcpy(buf, out.data(), bytes, hipMemcpyHostToDevice)) != hipSuccess
+                 || (st && (he = hipStreamSynchronize(st)) != hipSuccess)) {
+            g->abort();
+            return ge::fail(GE_ERR_HIP, "local all-reduce: copy to the device failed: %s", hipGetErrorString(he));
+        }
+        return GE_OK;
+    }
+    ge_status sum_f32(float *d, int64_t n, hipStream_t st = nullptr) {
+        return run(d, n, false, st, [&](float *o, auto stage) { for (int64_t k = 0; k < n; ++k) { float a = 0.0f; for (int r = 0; r < g->world; ++r) a += stage(r)[k]; o[k] = a; } });
+    }
+    ge_status sum_bf16(uint16_t *d, int64_t n) {                   // summed in fp32, rounded to nearest even
+        return run(d, n, false, nullptr, [&](uint16_t *o, auto stage) {
+            for (int64_t k = 0; k < n; ++k) { float a = 0.0f; for (int r = 0; r < g->world; ++r) a += bf16_to_f32(stage(r)[k]); o[k] = (uint16_t)f32_to_bf16_rne(a); }
+        });
+    }
+    ge_status start(const std::vector<Entry *> &taken) override {
+        ge_status st = wire_from_own(main, taken);
+        for (Entry *e : taken) {
+            if (st == GE_OK) st = e->w16 ? sum_bf16((uint16_t *)e->wire, e->n) : sum_f32((float *)e->wire, e->n);
+            if (st == GE_OK && e->mean) st = sum_f32(e->cnt, e->n);
+        }
+        return st;
+    }
+    ge_status wait(std::vector<Entry> &) override { return GE_OK; }
+    ge_status sum_small(float *d, int64_t n) override { GE_HIP(hipStreamSynchronize(main)); return sum_f32(d, n); }
+    ge_status sum_live(float *d, int64_t n, hipStream_t st) override { GE_HIP(hipStreamSynchronize(st)); return sum_f32(d, n, st); }
+    ge_status broadcast(float *d, int64_t n, int32_t src) override {
+        GE_HIP(hipStreamSynchronize(main));
+        return run(d, n, false, nullptr, [&](float *o, auto stage) { std::memcpy(o, stage(src), sizeof(float) * (size_t)n); });
+    }
+    ge_status reduce_f64(double *v, int32_t n, bool max) override {          // from rank 0's value
+        return run(v, n, true, nullptr, [&](double *o, auto stage) {
+            for (int32_t k = 0; k < n; ++k) { o[k] = stage(0)[k]; for (int r = 1; r < g->world; ++r) o[k] = max ? std::max(o[k], stage(r)[k]) : o[k] + stage(r)[k]; }
+        });
+    }
+    void abort() override { g->abort(); }
+};
+
+// The host's callbacks (ge_transport): device buffers, handed over once main is drained.  Nothing beside the epoch kernel, no host scalars.
+struct HostCollective final : Collective {
+    ge_transport tr;
+    HostCollective(hipStream_t m, const ge_transport &t) : Collective(m), tr(t) {}
+    ge_status start(const std::vector<Entry *> &taken) override {
+        ge_status st = wire_from_own(main, taken);
+        if (st != GE_OK) return st;
+        for (Entry *e : taken) {
+            st = tr.start(tr.user, e->wire, e->n, e->w16 ? GE_DTYPE_BF16 : GE_DTYPE_F32, &e->ticket);
+            if (st == GE_OK && e->mean) st = tr.start(tr.user, e->cnt, e->n, GE_DTYPE_F32, &e->ticket_cnt);
+            if (st != GE_OK) return ge::fail(st, "transport.start failed for %s", e->name);
+        }
+        return GE_OK;
+    }
+    ge_status wait(std::vector<Entry> &ent) override {
+        for (Entry &e : ent) {
+            if (!e.in_flight) continue;
+            ge_status st = tr.wait(tr.user, e.ticket);
+            if (st == GE_OK && e.mean) st = tr.wait(tr.user, e.ticket_cnt);
+            if (st != GE_OK) return ge::fail(st, "transport.wait failed for %s", e.name);
+        }
+        return GE_OK;
+    }
+    ge_status sum_small(float *d, int64_t n) override {
+        GE_HIP(hipStreamSynchronize(main));
+        void *t = nullptr; ge_status st = tr.start(tr.user, d, n, GE_DTYPE_F32, &t);
+        if (st == GE_OK) st = tr.wait(tr.user, t);
+        return st == GE_OK ? GE_OK : ge::fail(st, "transport failed for the hub rows");
+    }
+    bool can_run_live() const override { return false; }
+    ge_status sum_live(float *, int64_t, hipStream_t) override { return ge::fail(GE_ERR_STATE, "a host transport cannot run beside the epoch kernel"); }
+    ge_status broadcast(float *d, int64_t n, int32_t src) override {
+        GE_HIP(hipStreamSynchronize(main));
+        const ge_status st = tr.broadcast(tr.user, d, n, GE_DTYPE_F32, src);
+        return st == GE_OK ? GE_OK : ge::fail(st, "transport.broadcast failed");
+    }
+    ge_status reduce_f64(double *, int32_t, bool) override { return ge::fail(GE_ERR_STATE, "ge_sync_allreduce_f64 runs over RCCL; a host that brought its own transport reduces its scalars there"); }
+};
 
 ge_status launch_turn(ge_sync *s, Entry &e, bool land, bool take) {
     if (!land && !take) return GE_OK;
@@ -491,15 +620,11 @@ ge_status launch_turn(ge_sync *s, Entry &e, bool land, bool take) {
     }
     if (!e.mean && e.cols % 4 == 0 && e.t_stride % 4 == 0 && ((uintptr_t)e.table % 16) == 0 && e.n / 4 < ((int64_t)1 << 31)) {       // the large tables
         const int64_t n4 = e.n / 4;
-        static const int per_cu = [] { const char *v = std::getenv("GE_SYNC_BLOCKS_PER_CU"); const int k = v ? std::atoi(v) : 0; return k > 0 ? k : 8; }();
-        const dim3 g4((unsigned)std::max<int64_t>(1, std::min<int64_t>((n4 + 1023) / 1024, (int64_t)s->cus * per_cu))), b4(256);
-        static const bool nt = [] { const char *v = std::getenv("GE_SYNC_NT"); return v ? std::atoi(v) != 0 : true; }();
+        const dim3 g4((unsigned)std::max<int64_t>(1, std::min<int64_t>((n4 + 1023) / 1024, (int64_t)s->cus * 8))), b4(256);
 #define GE_TURN4(L, T)                                                                                                              \
         do {                                                                                                                        \
-            if (e.w16 && nt) hipLaunchKernelGGL((k_sync_turn_flat4<L, T, true, true>), g4, b4, 0, s->main, e.table, e.t_stride, (uint32_t)(e.cols / 4), (uint32_t)n4, e.base, e.wire, e.own); \
-            else if (e.w16) hipLaunchKernelGGL((k_sync_turn_flat4<L, T, true, false>), g4, b4, 0, s->main, e.table, e.t_stride, (uint32_t)(e.cols / 4), (uint32_t)n4, e.base, e.wire, e.own); \
-            else if (nt) hipLaunchKernelGGL((k_sync_turn_flat4<L, T, false, true>), g4, b4, 0, s->main, e.table, e.t_stride, (uint32_t)(e.cols / 4), (uint32_t)n4, e.base, e.wire, e.own); \
-            else hipLaunchKernelGGL((k_sync_turn_flat4<L, T, false, false>), g4, b4, 0, s->main, e.table, e.t_stride, (uint32_t)(e.cols / 4), (uint32_t)n4, e.base, e.wire, e.own); \
+            if (e.w16) hipLaunchKernelGGL((k_sync_turn_flat4<L, T, true>), g4, b4, 0, s->main, e.table, e.t_stride, (uint32_t)(e.cols / 4), (uint32_t)n4, e.base, e.wire, e.own); \
+            else hipLaunchKernelGGL((k_sync_turn_flat4<L, T, false>), g4, b4, 0, s->main, e.table, e.t_stride, (uint32_t)(e.cols / 4), (uint32_t)n4, e.base, e.wire, e.own); \
         } while (0)
         if (land && take) GE_TURN4(true, true); else if (land) GE_TURN4(true, false); else GE_TURN4(false, true);
 #undef GE_TURN4
@@ -519,72 +644,13 @@ ge_status launch_turn(ge_sync *s, Entry &e, bool land, bool take) {
     return GE_OK;
 }
 
-// starts the all-reduce of every entry taken in this call
-ge_status start_reduce(ge_sync *s, const std::vector<Entry *> &taken) {
-    if (taken.empty()) return GE_OK;
-    // the transports that sum in place (local group, the host's callbacks) get the send buffer copied into the receive buffer
-    // first; RCCL reduces out of place, own -> wire
-    if (s->loop || s->tr.start)
-        for (Entry *e : taken) GE_HIP(hipMemcpyAsync(e->wire, e->own, (size_t)e->n * (e->w16 ? 2 : 4), hipMemcpyDeviceToDevice, s->main));
-    if (s->loop) {
-        GE_HIP(hipStreamSynchronize(s->main));
-        for (Entry *e : taken) {
-            ge_status st = local_allreduce(s->loop, s->cfg.rank, e->wire, e->n, e->w16 ? GE_DTYPE_BF16 : GE_DTYPE_F32, false, 0);
-            if (st == GE_OK && e->mean) st = local_allreduce(s->loop, s->cfg.rank, e->cnt, e->n, GE_DTYPE_F32, false, 0);
-            if (st != GE_OK) return st;
-        }
-    } else if (!s->tr.start) {
-        GE_HIP(hipEventRecord(s->ev_taken, s->main));
-        GE_HIP(hipStreamWaitEvent(s->side, s->ev_taken, 0));
-        for (Entry *e : taken) {
-            GE_NCCL(rccl().AllReduce(e->own, e->wire, (size_t)e->n, e->w16 ? ncclBfloat16 : ncclFloat32, ncclSum, s->comm, s->side));
-            if (e->mean) GE_NCCL(rccl().AllReduce(e->cnt, e->cnt, (size_t)e->n, ncclFloat32, ncclSum, s->comm, s->side));
-        }
-        GE_HIP(hipEventRecord(s->ev_reduced, s->side));
-    } else {
-        GE_HIP(hipStreamSynchronize(s->main));                          // the host's collective reads the buffers
-        for (Entry *e : taken) {
-            ge_status st = s->tr.start(s->tr.user, e->wire, e->n, e->w16 ? GE_DTYPE_BF16 : GE_DTYPE_F32, &e->ticket);
-            if (st == GE_OK && e->mean) st = s->tr.start(s->tr.user, e->cnt, e->n, GE_DTYPE_F32, &e->ticket_cnt);
-            if (st != GE_OK) return ge::fail(st, "transport.start failed for %s", e->name);
-        }
-    }
-    for (Entry *e : taken) e->in_flight = true;
-    return GE_OK;
-}
-
-ge_status wait_reduce(ge_sync *s) {
-    bool any = false;
-    for (Entry &e : s->ent) any = any || e.in_flight;
-    if (!any || s->loop) return GE_OK;
-    if (!s->tr.start) { GE_HIP(hipStreamWaitEvent(s->main, s->ev_reduced, 0)); return GE_OK; }
-    for (Entry &e : s->ent) {
-        if (!e.in_flight) continue;
-        ge_status st = s->tr.wait(s->tr.user, e.ticket);
-        if (st == GE_OK && e.mean) st = s->tr.wait(s->tr.user, e.ticket_cnt);
-        if (st != GE_OK) return ge::fail(st, "transport.wait failed for %s", e.name);
-    }
-    return GE_OK;
-}
-
-// sum of a small fp32 device buffer over the ranks, ordered on the handle's stream (RCCL: asynchronous, on the hub stream)
-ge_status allreduce_f32_small(ge_sync *s, float *dbuf, int64_t n) {
-    if (s->loop) {
-        GE_HIP(hipStreamSynchronize(s->main));
-        return local_allreduce(s->loop, s->cfg.rank, dbuf, n, GE_DTYPE_F32, false, 0);
-    }
-    if (s->tr.start) {
-        GE_HIP(hipStreamSynchronize(s->main));
-        void *t = nullptr;
-        ge_status st = s->tr.start(s->tr.user, dbuf, n, GE_DTYPE_F32, &t);
-        if (st == GE_OK) st = s->tr.wait(s->tr.user, t);
-        return st == GE_OK ? GE_OK : ge::fail(st, "transport failed for the hub rows");
-    }
-    GE_HIP(hipEventRecord(s->ev_hub_a, s->main));
-    GE_HIP(hipStreamWaitEvent(s->hub_side, s->ev_hub_a, 0));
-    GE_NCCL(rccl().AllReduce(dbuf, dbuf, (size_t)n, ncclFloat32, ncclSum, s->hub_comm, s->hub_side));
-    GE_HIP(hipEventRecord(s->ev_hub_b, s->hub_side));
-    GE_HIP(hipStreamWaitEvent(s->main, s->ev_hub_b, 0));
+// n floats of d (first uploaded from `in`, if given) summed over the ranks and read back into `out`; blocking
+ge_status sum_to_host(ge_sync *s, float *d, int64_t n, float *out, const float *in = nullptr) {
+    if (in) { GE_HIP(hipMemcpyAsync(d, in, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, s->main)); GE_HIP(hipStreamSynchronize(s->main)); }
+    const ge_status st = s->coll->sum_small(d, n);
+    if (st != GE_OK) return st;
+    GE_HIP(hipMemcpyAsync(out, d, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, s->main));
+    GE_HIP(hipStreamSynchronize(s->main));
     return GE_OK;
 }
 
@@ -602,7 +668,7 @@ ge_status hub_exchange(ge_sync *s) {
     else hipLaunchKernelGGL(k_hub_take<false>, g, b, 0, s->main, s->hub_list, H, D, rows, rstride, er.base, (const float *)nullptr, (const int32_t *)nullptr, ea.table, ea.t_stride, ea.base,
                             eab.table, eab.t_stride, eab.base, eb.table, eb.t_stride, eb.base, s->hub_buf);
     GE_HIP(hipGetLastError());
-    ge_status st = allreduce_f32_small(s, s->hub_buf, (int64_t)H * (2 * D + 3));
+    ge_status st = s->coll->sum_small(s->hub_buf, (int64_t)H * (2 * D + 3));
     if (st != GE_OK) return st;
     s->seed = s->seed * 1664525u + 1013904223u;
     const uint32_t seed = s->seed ^ ((uint32_t)s->cfg.rank * 0x9E3779B1u);
@@ -625,12 +691,8 @@ ge_status live_exchange(ge_sync *s) {
                        r16 ? (const float *)s->lay.hub_rows : (const float *)nullptr, r16 ? s->lay.hub_index : (const int32_t *)nullptr, (const float *)er.base,
                        (const float *)ea.table, ea.t_stride, (const float *)ea.base, s->live_buf, s->live_own);
     GE_HIP(hipGetLastError());
-    const int64_t n = (int64_t)H * 2 * D;
-    if (s->loop) {
-        GE_HIP(hipStreamSynchronize(s->hub_side));
-        ge_status st = local_allreduce(s->loop, s->cfg.rank, s->live_buf, n, GE_DTYPE_F32, false, 0, s->hub_side);
-        if (st != GE_OK) return st;
-    } else GE_NCCL(rccl().AllReduce(s->live_buf, s->live_buf, (size_t)n, ncclFloat32, ncclSum, s->hub_comm, s->hub_side));
+    const ge_status st = s->coll->sum_live(s->live_buf, (int64_t)H * 2 * D, s->hub_side);
+    if (st != GE_OK) return st;
     hipLaunchKernelGGL(k_live_land, g, b, 0, s->hub_side, (const int32_t *)s->live_list, H, D, er.table, er.t_stride,
                        r16 ? s->lay.hub_rows : (float *)nullptr, r16 ? s->lay.hub_index : (const int32_t *)nullptr, er.base, ea.table, ea.t_stride, ea.base,
                        (const float *)s->live_buf, (const float *)s->live_own, s->merge_inv_world);
@@ -664,7 +726,7 @@ ge_status turn(ge_sync *s, bool land, bool take, bool everything) {
     bool due = false;
     if (take) { ++s->calls; due = everything || s->calls % std::max(1, s->cfg.accum_every) == 0; }
     if (take && !land) for (Entry &e : s->ent) if (e.in_flight) return ge::fail(GE_ERR_STATE, "ge_sync: finish the exchange in flight first");
-    if (land) { ge_status st = wait_reduce(s); if (st != GE_OK) return st; }
+    if (land && std::any_of(s->ent.begin(), s->ent.end(), [](const Entry &e) { return e.in_flight; })) { ge_status st = s->coll->wait(s->ent); if (st != GE_OK) return st; }
     std::vector<Entry *> taken;
     for (Entry &e : s->ent) {
         const bool do_land = land && e.in_flight, do_take = take && (due || !e.lazy);
@@ -673,7 +735,16 @@ ge_status turn(ge_sync *s, bool land, bool take, bool everything) {
         if (do_land) e.in_flight = false;
         if (do_take) taken.push_back(&e);
     }
-    return start_reduce(s, taken);
+    const ge_status st = taken.empty() ? GE_OK : s->coll->start(taken);     // the all-reduce of every entry taken in this call
+    if (st == GE_OK) for (Entry *e : taken) e->in_flight = true;
+    return st;
+}
+
+// The ge_sync_* calls that exchange: GE_GUARD, and a rank that fails inside one aborts its transport (a local group's peers return GE_ERR_STATE)
+template <typename F> ge_status with_abort(ge_sync *s, F body) {
+    const ge_status st = [&]() -> ge_status { GE_GUARD(body()); }();
+    if (st != GE_OK && s && s->coll) s->coll->abort();
+    return st;
 }
 
 }  // namespace
@@ -703,60 +774,55 @@ ge_status ge_rccl_unique_id(void *id128) {
     return GE_OK;
 }
 
-// One rank, one GPU: RCCL is opened, a communicator of size 1 made, a sum and a broadcast run through it and compared
-// with what went in.  What a single-GPU box can check of the RCCL path (symbols, calling convention, stream order).
-ge_status ge_rccl_selftest(int32_t device) {
-    ge_status st = ge::select_device(device);
-    if (st != GE_OK) return st;
-    if (!rccl().ok) return ge::fail(GE_ERR_HIP, "RCCL is not available (librccl.so.1 could not be loaded)");
+// One rank, one GPU: the RCCL transport ge_sync runs, on a communicator of size 1 and its split for the hub rows, through every operation
+// -- start / wait on an fp32 entry with counts and a bf16 entry, sum_small, sum_live and broadcast on the result, the f64 sum and max --
+// and the data compared with what went in: what a single-GPU box can check of the RCCL path (symbols, calling convention, stream order).
+static ge_status rccl_selftest(int32_t device) {
     ncclUniqueId id;
-    GE_NCCL(rccl().GetUniqueId(&id));
-    ncclComm_t comm = nullptr;
-    GE_NCCL(rccl().CommInitRank(&comm, 1, id, 0));
-    const int n = 4096;
-    float *d = nullptr; hipStream_t side = nullptr;
-    std::vector<float> h((size_t)n), back((size_t)n);
-    for (int k = 0; k < n; ++k) h[(size_t)k] = 0.25f * (float)k - 7.0f;
-    hipError_t he = hipMalloc((void **)&d, sizeof(float) * n);
-    if (he == hipSuccess) he = hipStreamCreateWithFlags(&side, hipStreamNonBlocking);
-    if (he == hipSuccess) he = hipMemcpyAsync(d, h.data(), sizeof(float) * n, hipMemcpyHostToDevice, side);
-    ncclResult_t nr = ncclSuccess;
-    if (he == hipSuccess) nr = rccl().AllReduce(d, d, (size_t)n, ncclFloat32, ncclSum, comm, side);
-    if (he == hipSuccess && nr == ncclSuccess) nr = rccl().Broadcast(d, d, (size_t)n, ncclFloat32, 0, comm, side);
-    ncclComm_t comm2 = nullptr;                      // the second communicator ge_sync makes for the hub rows (ncclCommSplit), used the same way
-    if (he == hipSuccess && nr == ncclSuccess && rccl().CommSplit) {
-        nr = rccl().CommSplit(comm, 0, 0, &comm2, nullptr);
-        if (nr == ncclSuccess && comm2) nr = rccl().AllReduce(d, d, (size_t)n, ncclFloat32, ncclSum, comm2, side);
-    }
-    if (he == hipSuccess && nr == ncclSuccess) he = hipMemcpyAsync(back.data(), d, sizeof(float) * n, hipMemcpyDeviceToHost, side);
-    if (he == hipSuccess && nr == ncclSuccess) he = hipStreamSynchronize(side);
-    if (d) (void)hipFree(d);
-    if (side) (void)hipStreamDestroy(side);
-    if (comm2) (void)rccl().CommDestroy(comm2);
-    (void)rccl().CommDestroy(comm);
-    if (nr != ncclSuccess) return ge::fail(GE_ERR_HIP, "RCCL self-test: %s", rccl().GetErrorString(nr));
-    if (he != hipSuccess) return ge::fail(GE_ERR_HIP, "RCCL self-test: %s", hipGetErrorString(he));
-    if (std::memcmp(h.data(), back.data(), sizeof(float) * n) != 0) return ge::fail(GE_ERR_STATE, "RCCL self-test: a one-rank sum changed the data");
+    ge_status st = ge::select_device(device);
+    if (st != GE_OK || (st = ge_rccl_unique_id(&id)) != GE_OK) return st;
+    const int64_t n = 4096; const size_t b4 = sizeof(float) * (size_t)n;
+    std::vector<float> h((size_t)n), back(3 * (size_t)n);
+    std::vector<uint16_t> h16((size_t)n);
+    for (size_t k = 0; k < (size_t)n; ++k) { h[k] = 0.25f * (float)k - 7.0f; h16[k] = (uint16_t)f32_to_bf16_rne(h[k]); }
+    struct Res { hipStream_t main = nullptr, hub_side = nullptr; float *mem = nullptr;
+                 ~Res() { for (hipStream_t q : {main, hub_side}) if (q) { (void)hipStreamSynchronize(q); (void)hipStreamDestroy(q); } if (mem) (void)hipFree(mem); } } res;
+    GE_HIP(hipStreamCreateWithFlags(&res.main, hipStreamNonBlocking));
+    GE_HIP(hipMalloc((void **)&res.mem, 4 * b4));
+    std::vector<Entry> ent(2); Entry &e32 = ent[0], &e16 = ent[1];   // [own | wire | cnt] fp32, [own | wire] bf16
+    e32.n = e16.n = n; e32.mean = e16.w16 = true;
+    e32.own = res.mem; e32.wire = res.mem + n; e32.cnt = res.mem + 2 * n; e16.own = res.mem + 3 * n; e16.wire = (uint16_t *)e16.own + n;
+    float *const w = (float *)e32.wire;
+    GE_HIP(hipMemcpyAsync(e32.own, h.data(), b4, hipMemcpyHostToDevice, res.main));
+    GE_HIP(hipMemcpyAsync(e32.cnt, h.data(), b4, hipMemcpyHostToDevice, res.main));
+    GE_HIP(hipMemcpyAsync(e16.own, h16.data(), b4 / 2, hipMemcpyHostToDevice, res.main));
+    RcclCollective r(res.main);                                     // (destroyed before res)
+    if ((st = r.init(1, 0, &id, &res.hub_side)) != GE_OK || (st = r.start({&e32, &e16})) != GE_OK || (st = r.wait(ent)) != GE_OK
+        || (st = r.sum_small(w, n)) != GE_OK || (st = r.sum_live(w, n, res.hub_side)) != GE_OK) return st;
+    GE_HIP(hipStreamSynchronize(res.hub_side));
+    if ((st = r.broadcast(w, n, 0)) != GE_OK) return st;
+    GE_HIP(hipMemcpyAsync(back.data(), w, 3 * b4, hipMemcpyDeviceToHost, res.main));   // wire, cnt, the bf16 entry
+    GE_HIP(hipStreamSynchronize(res.main));
+    const double want[3] = {1.5, -2.25, 3.0e300};
+    double v[3] = {want[0], want[1], want[2]};
+    if ((st = r.reduce_f64(v, 3, false)) != GE_OK || (st = r.reduce_f64(v, 3, true)) != GE_OK) return st;
+    if (std::memcmp(back.data(), h.data(), b4) || std::memcmp(back.data() + n, h.data(), b4) || std::memcmp((uint16_t *)(back.data() + 2 * n) + n, h16.data(), b4 / 2)
+        || std::memcmp(v, want, sizeof(v)))
+        return ge::fail(GE_ERR_STATE, "RCCL self-test: a one-rank exchange changed the data");
     return GE_OK;
 }
+ge_status ge_rccl_selftest(int32_t device) { GE_GUARD(rccl_selftest(device)); }
 
 void ge_sync_destroy(ge_sync *s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
     if (s->main) (void)hipStreamSynchronize(s->main);
-    if (s->side) (void)hipStreamSynchronize(s->side);
     if (s->hub_side) (void)hipStreamSynchronize(s->hub_side);
-    if (s->hub_comm && s->hub_comm != s->comm && rccl().ok) (void)rccl().CommDestroy(s->hub_comm);
-    if (s->comm && rccl().ok) (void)rccl().CommDestroy(s->comm);
+    s->coll.reset();                                               // (RCCL: its stream drained, the hub rows' communicator destroyed before the first)
     if (s->ev_reset) (void)hipEventDestroy(s->ev_reset);
     if (s->progress) (void)hipHostFree(s->progress);
-    if (s->ev_hub_a) (void)hipEventDestroy(s->ev_hub_a);
-    if (s->ev_hub_b) (void)hipEventDestroy(s->ev_hub_b);
     if (s->hub_side) (void)hipStreamDestroy(s->hub_side);
     for (void *q : s->owned) (void)hipFree(q);
-    if (s->ev_taken) (void)hipEventDestroy(s->ev_taken);
-    if (s->ev_reduced) (void)hipEventDestroy(s->ev_reduced);
-    if (s->side) (void)hipStreamDestroy(s->side);
     delete s;
 }
 
@@ -776,12 +842,10 @@ static ge_status ge_sync_create_impl(ge_glove *h, const ge_sync_cfg *cfg, ge_syn
     ge_sync *s = new (std::nothrow) ge_sync();
     if (!s) return ge::fail(GE_ERR_OOM, "host allocation failed");
     s->h = h; s->cfg = *cfg; s->cfg.transport = nullptr; s->cfg.rccl_id = nullptr; s->cfg.local_group = nullptr;
-    s->loop = cfg->local_group;
-    if (s->loop && s->loop->world != cfg->world) { delete s; return ge::fail(GE_ERR_ARG, "local group has %d ranks, cfg.world is %d", s->loop->world, cfg->world); }
+    if (cfg->local_group && cfg->local_group->world != cfg->world) { delete s; return ge::fail(GE_ERR_ARG, "local group has %d ranks, cfg.world is %d", cfg->local_group->world, cfg->world); }
     if (s->cfg.accum_every == 0) s->cfg.accum_every = 4;
     s->merge_inv_world = 1.0f / (float)std::max(1, cfg->world);
     if (const char *e = std::getenv("GE_SYNC_MERGE")) if (std::strcmp(e, "sum") == 0) s->merge_inv_world = 0.0f;        // experiments: the hub rows' deltas summed as they are
-    if (cfg->transport) s->tr = *cfg->transport;
     s->main = (hipStream_t)stream; s->device = device;
 #define GE_TRYS(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { ge_status _s = ge::fail(_e == hipErrorOutOfMemory ? GE_ERR_OOM : GE_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); ge_sync_destroy(s); return _s; } } while (0)
     GE_TRYS(hipSetDevice(device));
@@ -816,29 +880,12 @@ static ge_status ge_sync_create_impl(ge_glove *h, const ge_sync_cfg *cfg, ge_syn
         }
         GE_TRYS(hipGetLastError());
         GE_TRYS(hipStreamSynchronize(s->main));
-        if (!s->tr.start && !s->loop) {
+        if (cfg->local_group) s->coll.reset(new LocalCollective(s->main, cfg->local_group, cfg->rank));
+        else if (cfg->transport) s->coll.reset(new HostCollective(s->main, *cfg->transport));
+        else {
             if (!cfg->rccl_id) { ge_sync_destroy(s); return ge::fail(GE_ERR_ARG, "world > 1 needs a transport, a local group or an RCCL unique id (ge_rccl_unique_id on rank 0, handed to every rank)"); }
-            if (!rccl().ok) { ge_sync_destroy(s); return ge::fail(GE_ERR_HIP, "RCCL is not available (librccl.so.1 could not be loaded)"); }
-            GE_TRYS(hipStreamCreateWithFlags(&s->side, hipStreamNonBlocking));
-            GE_TRYS(hipEventCreateWithFlags(&s->ev_taken, hipEventDisableTiming));
-            GE_TRYS(hipEventCreateWithFlags(&s->ev_reduced, hipEventDisableTiming));
-            ncclUniqueId id; std::memcpy(&id, cfg->rccl_id, sizeof(id));
-            ncclResult_t r = rccl().CommInitRank(&s->comm, cfg->world, id, cfg->rank);
-            if (r != ncclSuccess) { ge_status e2 = ge::fail(GE_ERR_HIP, "ncclCommInitRank failed: %s", rccl().GetErrorString(r)); s->comm = nullptr; ge_sync_destroy(s); return e2; }
-            GE_TRYS(hipStreamCreateWithFlags(&s->hub_side, hipStreamNonBlocking));
-            GE_TRYS(hipEventCreateWithFlags(&s->ev_hub_a, hipEventDisableTiming));
-            GE_TRYS(hipEventCreateWithFlags(&s->ev_hub_b, hipEventDisableTiming));
-            // The hub rows' communicator: a split of the first one (every rank makes the same choice: the symbol is there or it is not,
-            // GE_SYNC_HUB_COMM=shared turns it off everywhere; a split that fails is an error, not a silent fallback that would leave
-            // the ranks on different communicators)
-            s->hub_comm = s->comm;
-            const char *hc = std::getenv("GE_SYNC_HUB_COMM");
-            if (rccl().CommSplit && !(hc && std::strcmp(hc, "shared") == 0)) {
-                ncclComm_t c2 = nullptr;
-                ncclResult_t r2 = rccl().CommSplit(s->comm, 0, cfg->rank, &c2, nullptr);
-                if (r2 != ncclSuccess || !c2) { ge_status e2 = ge::fail(GE_ERR_HIP, "ncclCommSplit failed: %s (GE_SYNC_HUB_COMM=shared uses one communicator)", rccl().GetErrorString(r2)); ge_sync_destroy(s); return e2; }
-                s->hub_comm = c2;
-            }
+            RcclCollective *r = new RcclCollective(s->main); s->coll.reset(r);
+            if ((st = r->init(cfg->world, cfg->rank, cfg->rccl_id, &s->hub_side)) != GE_OK) { ge_sync_destroy(s); return st; }
         }
         // The hub rows of the small exchanges (ge_sync_epoch): the union of the ranks' busy columns -- count on the rank >= max(256,
         // N_rank / 20 480), whatever the handle's worker count or hot-column setting (every rank flags its own in a [V] vector, the
@@ -862,11 +909,8 @@ static ge_status ge_sync_create_impl(ge_glove *h, const ge_sync_cfg *cfg, ge_syn
                 GE_TRYS(hipMemcpyAsync(tmp_n, mine_n->data(), sizeof(int32_t) * (size_t)nm, hipMemcpyHostToDevice, s->main));
                 hipLaunchKernelGGL(k_mark, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, s->main, (const int32_t *)tmp, (const int32_t *)tmp_n, nm, flags);
             }
-            st = allreduce_f32_small(s, flags, V);
-            if (st != GE_OK) { ge_sync_destroy(s); return st; }
             std::vector<float> hf((size_t)V);
-            GE_TRYS(hipMemcpyAsync(hf.data(), flags, sizeof(float) * (size_t)V, hipMemcpyDeviceToHost, s->main));
-            GE_TRYS(hipStreamSynchronize(s->main));
+            if ((st = sum_to_host(s, flags, V, hf.data())) != GE_OK) { ge_sync_destroy(s); return st; }
             std::vector<int32_t> all;
             for (int64_t v = 0; v < V; ++v) if (hf[(size_t)v] > 0.0f) { all.push_back((int32_t)v); s->hub_top_count = std::max(s->hub_top_count, hf[(size_t)v]); }
             s->n_hub = (int32_t)all.size();
@@ -886,15 +930,10 @@ static ge_status ge_sync_create_impl(ge_glove *h, const ge_sync_cfg *cfg, ge_syn
             const std::vector<int32_t> *kh = ge::glove_kernel_hubs(h);
             bool mine_ok = kh != nullptr;
             if (mine_ok && mine) for (int32_t v : *mine) if (!std::binary_search(kh->begin(), kh->end(), v)) { mine_ok = false; break; }
-            const bool can = !s->tr.start && !(mode_env && std::strcmp(mode_env, "segments") == 0) && s->n_hub > 0;
+            const bool can = s->coll->can_run_live() && !(mode_env && std::strcmp(mode_env, "segments") == 0) && s->n_hub > 0;
             const float vote = (can && mine_ok) ? 0.0f : 1.0f;
-            GE_TRYS(hipMemcpyAsync(flags, &vote, sizeof(float), hipMemcpyHostToDevice, s->main));
-            GE_TRYS(hipStreamSynchronize(s->main));
-            st = allreduce_f32_small(s, flags, 1);
-            if (st != GE_OK) { ge_sync_destroy(s); return st; }
             float against = 1.0f;
-            GE_TRYS(hipMemcpyAsync(&against, flags, sizeof(float), hipMemcpyDeviceToHost, s->main));
-            GE_TRYS(hipStreamSynchronize(s->main));
+            if ((st = sum_to_host(s, flags, 1, &against, &vote)) != GE_OK) { ge_sync_destroy(s); return st; }
             if (against == 0.0f && s->lay.dtype == GE_DTYPE_BF16) {
                 // bf16 rows: a hub row lives in an fp32 master row that the kernel moves by atomics -- where the column is a hub of the rank.
                 // The live set is therefore the columns that are hubs on EVERY rank; the few columns at the threshold that are not get
@@ -908,10 +947,7 @@ static ge_status ge_sync_create_impl(ge_glove *h, const ge_sync_cfg *cfg, ge_syn
                     GE_TRYS(hipMemcpyAsync(tk, kh->data(), sizeof(int32_t) * (size_t)nk, hipMemcpyHostToDevice, s->main));
                     hipLaunchKernelGGL(k_mark, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, s->main, (const int32_t *)tk, (const int32_t *)nullptr, nk, flags);
                 }
-                st = allreduce_f32_small(s, flags, V);
-                if (st != GE_OK) { ge_sync_destroy(s); return st; }
-                GE_TRYS(hipMemcpyAsync(hf.data(), flags, sizeof(float) * (size_t)V, hipMemcpyDeviceToHost, s->main));
-                GE_TRYS(hipStreamSynchronize(s->main));
+                if ((st = sum_to_host(s, flags, V, hf.data())) != GE_OK) { ge_sync_destroy(s); return st; }
                 std::vector<int32_t> lv;
                 for (int32_t v : all) if (hf[(size_t)v] == (float)cfg->world) lv.push_back(v);
                 s->n_live = (int32_t)lv.size();
@@ -936,13 +972,9 @@ static ge_status ge_sync_create_impl(ge_glove *h, const ge_sync_cfg *cfg, ge_syn
 }
 ge_status ge_sync_create(ge_glove *h, const ge_sync_cfg *cfg, ge_sync **out) { GE_GUARD(ge_sync_create_impl(h, cfg, out)); }
 
-// a rank of a local group that fails inside an exchange call takes the group down with it: its peers' barriers return
-// GE_ERR_STATE instead of waiting for a rank that will not come
-static ge_status with_abort(ge_sync *s, ge_status st) { if (st != GE_OK && s && s->loop) s->loop->abort(); return st; }
-static ge_status turn_guarded(ge_sync *s, bool land, bool take, bool everything) { GE_GUARD(turn(s, land, take, everything)); }
-ge_status ge_sync_begin(ge_sync *s, int32_t everything) { return with_abort(s, turn_guarded(s, false, true, everything != 0)); }
-ge_status ge_sync_finish(ge_sync *s) { return with_abort(s, turn_guarded(s, true, false, false)); }
-ge_status ge_sync_turn(ge_sync *s) { return with_abort(s, turn_guarded(s, true, true, false)); }
+ge_status ge_sync_begin(ge_sync *s, int32_t everything) { return with_abort(s, [&] { return turn(s, false, true, everything != 0); }); }
+ge_status ge_sync_finish(ge_sync *s) { return with_abort(s, [&] { return turn(s, true, false, false); }); }
+ge_status ge_sync_turn(ge_sync *s) { return with_abort(s, [&] { return turn(s, true, true, false); }); }
 ge_status ge_sync_sync(ge_sync *s) {          // lands what an earlier turn left in flight, takes, lands: nothing is in flight afterwards
     ge_status st = ge_sync_turn(s);
     return st == GE_OK ? ge_sync_finish(s) : st;
@@ -1008,12 +1040,8 @@ static ge_status ge_sync_epoch_impl(ge_sync *s, int32_t iteration, int32_t segme
     // ranks therefore vote after every live epoch: a quarter of the exchanges late on half of the ranks in two epochs running, and the run continues
     // in segments (the epoch then waits for every exchange).  One word, summed, on the exact exchange's path.
     const float mine_late = (late * 4 > S) ? 1.0f : 0.0f;
-    GE_HIP(hipMemcpyAsync(s->hub_buf, &mine_late, sizeof(float), hipMemcpyHostToDevice, s->main));
-    GE_HIP(hipStreamSynchronize(s->main));
-    if ((st = allreduce_f32_small(s, s->hub_buf, 1)) != GE_OK) return st;
     float any_late = 0.0f;
-    GE_HIP(hipMemcpyAsync(&any_late, s->hub_buf, sizeof(float), hipMemcpyDeviceToHost, s->main));
-    GE_HIP(hipStreamSynchronize(s->main));
+    if ((st = sum_to_host(s, s->hub_buf, 1, &any_late, &mine_late)) != GE_OK) return st;
     s->live_epochs += 1; s->live_late += late;
     // (half of the ranks or more: a single rank whose shard is small ends its kernel early and issues its exchanges "late" without any harm --
     // a transport that is too slow makes every rank late)
@@ -1041,17 +1069,16 @@ static ge_status ge_sync_hub_rows_impl(ge_sync *s, int32_t *out, int32_t capacit
     return GE_OK;
 }
 ge_status ge_sync_hub_rows(ge_sync *s, int32_t *out, int32_t capacity, int32_t *count) { GE_GUARD(ge_sync_hub_rows_impl(s, out, capacity, count)); }
-static ge_status hub_exchange_guarded(ge_sync *s) {
-    try {
+ge_status ge_sync_hub_exchange(ge_sync *s) {
+    return with_abort(s, [&]() -> ge_status {
         if (!s) return ge::fail(GE_ERR_ARG, "null ge_sync handle");
         if (s->cfg.world == 1) return GE_OK;
         GE_HIP(hipSetDevice(s->device));
         return hub_exchange(s);
-    } catch (const std::exception &e) { return ge::fail(GE_ERR_STATE, "internal error: %s", e.what()); }
+    });
 }
-ge_status ge_sync_hub_exchange(ge_sync *s) { return with_abort(s, hub_exchange_guarded(s)); }
-static ge_status live_exchange_guarded(ge_sync *s) {
-    try {
+ge_status ge_sync_hub_exchange_live(ge_sync *s) {
+    return with_abort(s, [&]() -> ge_status {
         if (!s) return ge::fail(GE_ERR_ARG, "null ge_sync handle");
         if (s->cfg.world == 1) return GE_OK;
         if (!s->live) return ge::fail(GE_ERR_STATE, "this run has no live hub rows (bf16 rows, a host transport, GE_SYNC_EPOCH=segments, or no column that is a hub on every rank)");
@@ -1059,9 +1086,8 @@ static ge_status live_exchange_guarded(ge_sync *s) {
         ge_status st = live_exchange(s);
         if (st == GE_OK) GE_HIP(hipStreamSynchronize(s->hub_side));
         return st;
-    } catch (const std::exception &e) { return ge::fail(GE_ERR_STATE, "internal error: %s", e.what()); }
+    });
 }
-ge_status ge_sync_hub_exchange_live(ge_sync *s) { return with_abort(s, live_exchange_guarded(s)); }
 ge_status ge_sync_live_rows(ge_sync *s, int32_t *out, int32_t capacity, int32_t *count) {
     if (!s || !count) return ge::fail(GE_ERR_ARG, "null argument");
     *count = s->live ? s->n_live : 0;
@@ -1081,8 +1107,7 @@ ge_status ge_sync_hub_plan(ge_sync *s, int32_t segments, int32_t *live, int32_t 
     return GE_OK;
 }
 
-static ge_status epoch_guarded(ge_sync *s, int32_t iteration, int32_t segments, double *cost_sum) { GE_GUARD(ge_sync_epoch_impl(s, iteration, segments, cost_sum)); }
-ge_status ge_sync_epoch(ge_sync *s, int32_t iteration, int32_t segments, double *cost_sum) { return with_abort(s, epoch_guarded(s, iteration, segments, cost_sum)); }
+ge_status ge_sync_epoch(ge_sync *s, int32_t iteration, int32_t segments, double *cost_sum) { return with_abort(s, [&] { return ge_sync_epoch_impl(s, iteration, segments, cost_sum); }); }
 
 static ge_status ge_sync_replicate_impl(ge_sync *s, int32_t src) {
     if (!s) return ge::fail(GE_ERR_ARG, "null ge_sync handle");
@@ -1099,20 +1124,7 @@ static ge_status ge_sync_replicate_impl(ge_sync *s, int32_t src) {
         float *tmp = nullptr;
         if (e.w16) { GE_HIP(hipMalloc((void **)&tmp, sizeof(float) * (size_t)e.n)); stage = tmp; }
         hipLaunchKernelGGL(k_gather, dim3(grid_for(e.n, s->cus)), dim3(256), 0, s->main, e.table, e.t_stride, e.cols, e.n, stage);
-        ge_status r = GE_OK;
-        if (s->loop) {
-            if (hipStreamSynchronize(s->main) != hipSuccess) r = ge::fail(GE_ERR_HIP, "replicate: stream synchronize failed");
-            else r = local_allreduce(s->loop, s->cfg.rank, stage, e.n, GE_DTYPE_F32, true, src);
-        } else if (!s->tr.start) {
-            hipError_t he = hipEventRecord(s->ev_taken, s->main);
-            if (he == hipSuccess) he = hipStreamWaitEvent(s->side, s->ev_taken, 0);
-            ncclResult_t nr = he == hipSuccess ? rccl().Broadcast(stage, stage, (size_t)e.n, ncclFloat32, src, s->comm, s->side) : ncclSuccess;
-            if (he == hipSuccess && nr == ncclSuccess) { he = hipEventRecord(s->ev_reduced, s->side); if (he == hipSuccess) he = hipStreamWaitEvent(s->main, s->ev_reduced, 0); }
-            if (he != hipSuccess || nr != ncclSuccess) r = ge::fail(GE_ERR_HIP, "replicate: broadcast of %s failed", e.name);
-        } else {
-            if (hipStreamSynchronize(s->main) != hipSuccess) r = ge::fail(GE_ERR_HIP, "replicate: stream synchronize failed");
-            else if ((r = s->tr.broadcast(s->tr.user, stage, e.n, GE_DTYPE_F32, src)) != GE_OK) r = ge::fail(r, "transport.broadcast failed for %s", e.name);
-        }
+        const ge_status r = s->coll->broadcast(stage, e.n, src);
         if (r == GE_OK) hipLaunchKernelGGL(k_scatter2, dim3(grid_for(e.n, s->cus)), dim3(256), 0, s->main, e.table, e.t_stride, e.cols, e.n, stage, e.base);
         hipError_t he = hipStreamSynchronize(s->main);
         if (tmp) (void)hipFree(tmp);
@@ -1121,31 +1133,18 @@ static ge_status ge_sync_replicate_impl(ge_sync *s, int32_t src) {
     }
     return GE_OK;
 }
-static ge_status replicate_guarded(ge_sync *s, int32_t src) { GE_GUARD(ge_sync_replicate_impl(s, src)); }
-ge_status ge_sync_replicate(ge_sync *s, int32_t src) { return with_abort(s, replicate_guarded(s, src)); }
+ge_status ge_sync_replicate(ge_sync *s, int32_t src) { return with_abort(s, [&] { return ge_sync_replicate_impl(s, src); }); }
 
 // Host scalars (the epoch's cost sums, a max over shards) over the same transport, so that a host without a
 // collective library of its own (the Java module) needs nothing else.  op: 0 = sum, 1 = max.  Blocking.
-static ge_status ge_sync_allreduce_f64_impl(ge_sync *s, double *values, int32_t n, int32_t op) {
-    if (!s || !values || n < 0) return ge::fail(GE_ERR_ARG, "invalid argument");
-    if (s->cfg.world == 1 || n == 0) return GE_OK;
-    if (op != 0 && op != 1) return ge::fail(GE_ERR_ARG, "op must be 0 (sum) or 1 (max)");
-    if (s->loop) return local_allreduce(s->loop, s->cfg.rank, values, n, 2, false, op);
-    if (s->tr.start) return ge::fail(GE_ERR_STATE, "ge_sync_allreduce_f64 runs over RCCL; a host that brought its own transport reduces its scalars there");
-    if (op != 0 && op != 1) return ge::fail(GE_ERR_ARG, "op must be 0 (sum) or 1 (max)");
-    GE_HIP(hipSetDevice(s->device));
-    double *d = nullptr;
-    GE_HIP(hipMalloc((void **)&d, sizeof(double) * (size_t)n));
-    hipError_t he = hipMemcpyAsync(d, values, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s->side);
-    ncclResult_t nr = he == hipSuccess ? rccl().AllReduce(d, d, (size_t)n, ncclFloat64, op == 0 ? ncclSum : ncclMax, s->comm, s->side) : ncclSuccess;
-    if (he == hipSuccess && nr == ncclSuccess) he = hipMemcpyAsync(values, d, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s->side);
-    if (he == hipSuccess && nr == ncclSuccess) he = hipStreamSynchronize(s->side);
-    (void)hipFree(d);
-    if (nr != ncclSuccess) return ge::fail(GE_ERR_HIP, "ncclAllReduce failed: %s", rccl().GetErrorString(nr));
-    if (he != hipSuccess) return ge::fail(GE_ERR_HIP, "scalar all-reduce: %s", hipGetErrorString(he));
-    return GE_OK;
+ge_status ge_sync_allreduce_f64(ge_sync *s, double *values, int32_t n, int32_t op) {
+    return with_abort(s, [&]() -> ge_status {
+        if (!s || !values || n < 0) return ge::fail(GE_ERR_ARG, "invalid argument");
+        if (s->cfg.world == 1 || n == 0) return GE_OK;
+        if (op != 0 && op != 1) return ge::fail(GE_ERR_ARG, "op must be 0 (sum) or 1 (max)");
+        GE_HIP(hipSetDevice(s->device));
+        return s->coll->reduce_f64(values, n, op == 1);
+    });
 }
-static ge_status allreduce_guarded(ge_sync *s, double *values, int32_t n, int32_t op) { GE_GUARD(ge_sync_allreduce_f64_impl(s, values, n, op)); }
-ge_status ge_sync_allreduce_f64(ge_sync *s, double *values, int32_t n, int32_t op) { return with_abort(s, allreduce_guarded(s, values, n, op)); }
 
 }  // extern "C"

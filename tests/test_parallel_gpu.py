@@ -318,7 +318,8 @@ def test_ge_sync_argument_errors(gpu):
 
 def test_rccl_path_runs_on_one_gpu(gpu):
     """RCCL refuses two ranks on one device, so a 1-GPU box cannot run the two-rank exchange over it; what it can run is the
-    library's RCCL binding itself: open librccl, ncclCommInitRank (one rank), ncclAllReduce + ncclBroadcast on a side stream,
+    RCCL transport ge_sync itself uses, on a one-rank communicator and its ncclCommSplit: the large exchange (an fp32 entry with
+    its counts and a bf16 entry, start / wait), the hub rows' small and live all-reduces, the broadcast and the f64 sum and max,
     data intact.  The N > 1 data path over RCCL is the driver's 8-GPU bench (bench.py --gpus N)."""
     from geglove import capi
     capi.check(capi.lib().ge_rccl_selftest(0))

@@ -62,6 +62,50 @@ def lane_dot(a, b, vw, nch):
     return wave_sum(part)
 
 
+def lane_shape(D):
+    """The lane shape pick_hogwild (csrc/glove.hip) gives a row of D floats: (vw, nch, fat) -- VW floats per lane, NCH register
+    chunks of 64 lanes, FAT when the bias lane (element D) lies inside the last chunk.  None where the kernel has no instance
+    (pick_hogwild returns nullptr: more than four chunks)."""
+    vw = 4 if D % 4 == 0 else 2 if D % 2 == 0 else 1
+    nch = (D + 64 * vw - 1) // (64 * vw)
+    if D < 1 or nch > 4:
+        return None
+    return vw, nch, (D // vw) % 64 != 0
+
+
+# The 16 fp32 lane shapes and the dims that pin each one: the smallest dim of the shape, and the dim that puts the bias in lane 63 of
+# the last chunk (a non-fat shape has one dim only: its lanes are full).  The bf16 instances are the VW 4 shapes.
+SHAPE_DIMS = {
+    (1, 1, True): (1, 63),     (1, 2, True): (65, 127),   (1, 3, True): (129, 191),  (1, 4, True): (193, 255),
+    (2, 1, True): (2, 126),    (2, 2, True): (130, 254),  (2, 3, True): (258, 382),  (2, 4, True): (386, 510),
+    (4, 1, True): (4, 252),    (4, 2, True): (260, 508),  (4, 3, True): (516, 764),  (4, 4, True): (772, 1020),
+    (4, 1, False): (256,),     (4, 2, False): (512,),     (4, 3, False): (768,),     (4, 4, False): (1024,),
+}
+SHAPE_TABLE_DIMS = sorted(d for dims in SHAPE_DIMS.values() for d in dims)
+LANE63_DIMS = sorted(max(dims) for dims in SHAPE_DIMS.values())            # bias in lane 63 (fat shapes), or the full-lane dim
+BF16_DIMS = [d for d in SHAPE_TABLE_DIMS if d % 4 == 0]
+OPTS = {0: "adagrad", 1: "adam", 2: "amsgrad"}                             # GE_OPT_*
+
+
+def instances(D):
+    """The k_adagrad_runs<VW, NCH, OPT, EMB16, FAT> instances a Hogwild handle of dim D can run: one per optimiser for fp32 rows,
+    plus the bf16 AdaGrad one where dim % 4 == 0.  Tuples (vw, nch, opt, emb16, fat)."""
+    s = lane_shape(D)
+    if s is None:
+        return []
+    vw, nch, fat = s
+    out = [(vw, nch, opt, False, fat) for opt in OPTS]
+    if D % 4 == 0:
+        out.append((4, nch, 0, True, fat))
+    return out
+
+
+def mangled(inst):
+    """The Itanium template-argument list of an instance: <4, 1, AdaGrad, fp32, fat> -> 'ILi4ELi1ELi0ELb0ELb1E'."""
+    vw, nch, opt, emb16, fat = inst
+    return "ILi%dELi%dELi%dELb%dELb%dE" % (vw, nch, opt, int(emb16), int(fat))
+
+
 def moment_step(amsgrad, corr, grad, m, v):
     """glove.hip moment_step, elementwise: returns (step, m', v')."""
     grad = np.asarray(grad, F32)
@@ -90,16 +134,23 @@ def adam_correction(lr, iteration):
     return F32(lr * np.sqrt(1 - b2 ** F64(iteration + 1)) / (1 - b1 ** F64(iteration + 1)))
 
 
-def moment_epoch(amsgrad, iteration, D, vw, nch, I, J, X, xmax, state, lr=0.05, pglove=False):
+def moment_epoch(amsgrad, iteration, D, vw, nch, I, J, X, xmax, state, lr=0.05, pglove=False, delta_runs=None):
     """One sequential pass over (I, J, X) in the given order on the 12-table state dict (2-D row tables, in place).  Returns the
-    cost sum (fp64, accumulated in walk order)."""
+    cost sum (fp64, accumulated in walk order).
+    delta_runs (per position, optional): label of the piece of a long focus row the nonzero belongs to, -1 elsewhere.  Such a piece
+    publishes its focus row by delta (close_run's RMW: the row a0 read at the piece's start, plus a - a0, in fp32), which differs from
+    storing a by up to an ulp of a per element."""
     corr = F32(lr) if amsgrad else adam_correction(lr, iteration)
     foc, ctx = state["focus"], state["context"]
     m1f, m1c, m2f, m2c = state["gsq_focus"], state["gsq_context"], state["m2_focus"], state["m2_context"]
     fb, cb = state["fbias"], state["cbias"]
     m1fb, m1cb, m2fb, m2cb = state["gsq_fbias"], state["gsq_cbias"], state["m2_fbias"], state["m2_cbias"]
     cost = 0.0
-    for i, j, x in zip(I.tolist(), J.tolist(), X.tolist()):
+    runs = [-1] * len(I) if delta_runs is None else list(delta_runs)
+    a0 = None
+    for k, (i, j, x) in enumerate(zip(I.tolist(), J.tolist(), X.tolist())):
+        if runs[k] >= 0 and (k == 0 or runs[k - 1] != runs[k]):
+            a0 = foc[i].copy()
         l, w = cost_terms(pglove, x, xmax)
         a, b = foc[i].copy(), ctx[j].copy()
         dot = lane_dot(a, b, vw, nch)
@@ -112,4 +163,20 @@ def moment_epoch(amsgrad, iteration, D, vw, nch, I, J, X, xmax, state, lr=0.05, 
         foc[i] = (a - st).astype(F32)
         st, m, v = moment_step(amsgrad, corr, wc, m1fb[i], m2fb[i]); fb[i] = F32(fb[i] - st); m1fb[i] = m; m2fb[i] = v
         st, m, v = moment_step(amsgrad, corr, wc, m1cb[j], m2cb[j]); cb[j] = F32(cb[j] - st); m1cb[j] = m; m2cb[j] = v
+        if runs[k] >= 0 and (k + 1 == len(runs) or runs[k + 1] != runs[k]):
+            foc[i] = (a0 + (foc[i] - a0).astype(F32)).astype(F32)
     return cost
+
+
+def long_row_pieces(I, order, chunk=128):
+    """delta_runs for moment_epoch: the blocked layout (csrc/glove_layout.hip) cuts an ordinary focus row of more than `chunk`
+    nonzeros into pieces of `chunk` in the caller's order; label each position of the walk `order` (caller indices) by its row's
+    piece (row * 2^20 + piece), -1 for rows stored whole.  For a layout without hub columns."""
+    I = np.asarray(I, np.int64)
+    count = np.bincount(I)
+    rank = np.zeros(len(I), np.int64)
+    seen = np.zeros(len(count), np.int64)
+    for k in range(len(I)):                                   # rank of nonzero k among its row's, in caller order
+        rank[k] = seen[I[k]]; seen[I[k]] += 1
+    o = np.asarray(order, np.int64)
+    return np.where(count[I[o]] > chunk, I[o] * (1 << 20) + rank[o] // chunk, -1)

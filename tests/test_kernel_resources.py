@@ -177,3 +177,53 @@ def test_trainer_kernel_instances_keep_their_state_in_registers():
     assert bench[0]["vgpr_count"] <= 96 and bench[0]["vgpr_spill_count"] == 0 and bench[0]["private_segment_fixed_size"] == 0, bench[0]
     # two LDS images per wave (row + accumulator row, 1 KB each) x 4 waves + the atomic strips: five workgroups fit a CU's 160 KB
     assert bench[0]["group_segment_fixed_size"] * 5 <= 160 * 1024, bench[0]
+
+
+def _reachable_instances():
+    """Every instance a Hogwild handle can run, from the lane-shape rule over every dim up to past the largest one accepted."""
+    import kernel_model as K
+    return {inst for D in range(1, 1100) for inst in K.instances(D)}
+
+
+def test_every_reachable_trainer_instance_is_in_the_code_object():
+    """pick_hogwild's 56 targets (16 lane shapes x 3 optimisers + 8 bf16 shapes) are all compiled for gfx950.  The 24 VW 1 / VW 2
+    instances without fat rows are compiled too but no dim reaches them (an odd dim, or twice an odd number, never fills 64 lanes)."""
+    import kernel_model as K
+    reach = _reachable_instances()
+    assert len(reach) == 56
+    assert len({i for i in reach if not i[3]}) == 48 and len({i for i in reach if i[3]}) == 8
+    names = [k for k in _kernel_metadata() if "k_adagrad_runs" in k]
+    for inst in sorted(reach):
+        hits = [k for k in names if K.mangled(inst) in k]
+        assert len(hits) == 1, (inst, K.mangled(inst), hits)
+    unreachable = [k for k in names if not any(K.mangled(i) in k for i in reach)]
+    assert len(unreachable) == len(names) - 56
+
+
+def test_shape_table_covers_every_reachable_instance():
+    """tests/kernel_model.py SHAPE_DIMS is what the GPU shape tests (test_kernel_shapes_gpu.py) iterate over: its dims reach all 56
+    instances, each dim sits in the shape it is listed under, and the lane-63 dims put the bias in the last lane of the last
+    chunk.  Leaving out the dims of any one shape leaves instances uncovered -- checked here for every shape."""
+    import kernel_model as K
+    reach = _reachable_instances()
+
+    def covered(dims):
+        return {inst for D in dims for inst in K.instances(D)}
+
+    assert covered(K.SHAPE_TABLE_DIMS) == reach
+    assert len(K.SHAPE_DIMS) == 16 and len(K.SHAPE_TABLE_DIMS) == 28
+    for shape, dims in K.SHAPE_DIMS.items():
+        vw, nch, fat = shape
+        for D in dims:
+            assert K.lane_shape(D) == shape, (D, shape)
+        assert dims[0] == min(D for D in range(1, 1100) if K.lane_shape(D) == shape), (shape, dims)      # the smallest dim of its shape
+        if fat:
+            assert (max(dims) // vw) % 64 == 63 and max(dims) // (64 * vw) == nch - 1, (shape, dims)
+        else:
+            assert dims == (256 * nch,)
+        others = [D for D in K.SHAPE_TABLE_DIMS if D not in dims]
+        assert covered(others) < reach, ("dropping", shape, "loses no instance")
+    # the largest dims accepted, and the first refused, of each vector width
+    assert K.lane_shape(255) == (1, 4, True) and K.lane_shape(257) is None
+    assert K.lane_shape(510) == (2, 4, True) and K.lane_shape(514) is None
+    assert K.lane_shape(1024) == (4, 4, False) and K.lane_shape(1028) is None

@@ -7,8 +7,10 @@ the timed region.  Weak scaling: every GPU owns ROWS_PER_GPU focus rows and ~NNZ
 the context factors are replicated and reconciled by an all-reduce of the per-rank deltas (RCCL) per step,
 so at 8 GPUs the job is BASELINE config C4 (5 M vertices / 1 B nonzeros / dim 200).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) carrying `roofline` and, at N=1,
-`cpu_baseline` (the oracle's restatement of Adagrad.createJob on the host cores, T = cores - 1 and T = 1).
+Prints ONE JSON line on rank 0 carrying `roofline`.  A plain run does only what that line's headline figure needs: set up, warm up,
+time the steps, dump the outputs if asked, print.  `--full` adds the measurements that take runs of their own, behind the timed region:
+at N=1 `cpu_baseline` (the oracle's restatement of Adagrad.createJob on the host cores, T = cores - 1 and T = 1), at N>1 the other
+exchange form (`exchange.other_form`), and `roofline.box_copy_GBps` (null in a plain run).
 
 roofline: `achieved` = bytes the kernel's schedule has to move per launch (ge_glove_info.schedule_bytes:
 per nonzero 20 B of matrix + the streamed row pair loaded and stored, per run the resident row pair loaded and
@@ -38,7 +40,10 @@ def parse():
     ap.add_argument("--rows-per-gpu", type=int, default=625_000)
     ap.add_argument("--nnz-per-gpu", type=int, default=125_000_000)
     ap.add_argument("--method", default="glove", choices=["glove", "pglove"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline (N=1), the other exchange form (N>1) "
+                         "and the box's copy bandwidth (roofline.box_copy_GBps)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--hot", default="auto", choices=["auto", "none", "all"])
     ap.add_argument("--hot-theta", type=float, default=0.0, help="column j is a hub when count(j) >= theta * N / workers (0 = the library default, 0.25)")
@@ -61,7 +66,7 @@ def parse():
                          "8 = BASELINE C4 at its own size, 5 M vertices / 0.86 G nonzeros); a recorded profile leg, not the default workload")
     ap.add_argument("--hub-segments", type=int, default=0,
                     help="N>1: small exchanges of the hub rows per epoch (ge_sync_epoch); 0 = the library's choice (by the busiest column; at least max(8, ranks)), -1 = none (one exchange per epoch for every row)")
-    ap.add_argument("--no-other-form", action="store_true", help="N>1: do not time the other exchange form behind the quoted region")
+    ap.add_argument("--no-other-form", action="store_true", help="N>1 with --full: do not time the other exchange form behind the quoted region")
     ap.add_argument("--accum-sync-every", type=int, default=4, help="every how many context syncs the AdaGrad accumulators are reconciled too (N>1)")
     ap.add_argument("--dump-outputs", metavar="DIR", default="",
                     help="rank 0, after the result line: replay the timed path reproducibly (one worker, a seeded sample of the nonzeros, "
@@ -298,11 +303,11 @@ def main():
     fence()
     dt = time.perf_counter() - t0
 
-    # N > 1: the OTHER exchange form on the same handles, timed the same way right behind the quoted region (the quoted `value`
-    # is the form --exchange names; a scaling record then holds both: the overlapped form is faster, the synchronous one
+    # N > 1 with --full: the OTHER exchange form on the same handles, timed the same way right behind the quoted region (the quoted
+    # `value` is the form --exchange names; a scaling record then holds both: the overlapped form is faster, the synchronous one
     # trains the better model per epoch).  The handle keeps its worker count (reserved slots) in both.
     other = None
-    if sync is not None and not args.no_other_form:
+    if sync is not None and args.full and not args.no_other_form:
         form2 = "sync" if args.exchange == "overlap" else "overlap"
         costs2, k_ms2, nl2 = [], 0.0, 0
         step(args.warmup + args.steps, form2); fence()          # one untimed step to change over
@@ -315,9 +320,9 @@ def main():
         other = {"exchange": form2, "dt": time.perf_counter() - t2, "costs": costs2, "kernel_ms": k_ms2 / max(args.steps, 1)}
 
     # what THIS box's memory system gives a plain device-to-device copy (1 GiB, read + written bytes), right after the timed
-    # region: boxes of the pool differ by 10-15 % in the epoch time of one binary, and this says which kind ran
+    # region: boxes of the pool differ by 10-15 % in the epoch time of one binary, and this says which kind ran (--full)
     box_copy = None
-    if rank == 0:
+    if rank == 0 and args.full:
         import ctypes
         g = ctypes.c_double(0.0)
         if capi.lib().ge_copy_bandwidth(local_rank, 1 << 30, 5, ctypes.byref(g)) == 0:
@@ -422,7 +427,7 @@ def main():
                                                  "kernel_ms_max_over_ranks": other["kernel_ms"],
                                                  "mean_cost_per_step": [c / n_global for c in other["costs"]],
                                                  "note": "the %d steps right behind the quoted region, same handles" % args.steps}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, V, D, I, J, X, xmax)
         print(json.dumps(out), flush=True)
         if args.dump_outputs:                 # behind the result line and every timed or exchanged step of every rank

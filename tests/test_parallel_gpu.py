@@ -579,12 +579,12 @@ def test_a_failing_rank_releases_its_local_group(gpu):
 def test_bench_starts_its_own_ranks(gpu):
     """`python3 bench.py --gpus 2` from a plain shell (no torchrun): the launcher starts both ranks before any GPU call.  On this
     one-GPU box they share device 0 over gloo (GE_BENCH_ONE_DEVICE / GE_BENCH_BACKEND, rehearsal switches); the line says n_gpus 2
-    and carries both exchange forms and the per-step cost of the whole job."""
+    and carries both exchange forms (the other one: --full) and the per-step cost of the whole job."""
     import json, subprocess, sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(GE_BENCH_BACKEND="gloo", GE_BENCH_ONE_DEVICE="1")
-    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
                         "--rows-per-gpu", "20000", "--nnz-per-gpu", "1500000"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -6,7 +6,7 @@ python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tai
 tail -1 $O/smoke.log
 for V in "d200:--dim 200" "d100:--dim 100" "d300:--dim 300" "d300bf16:--dim 300 --dtype bf16" "d200bf16:--dim 200 --dtype bf16" "adam:--opt adam" "pglove:--method pglove"; do
   name=${V%%:*}; args=${V#*:}
-  python3 bench.py --no-cpu-baseline --steps 5 $args > $O/$name.json 2> $O/$name.err || { tail -5 $O/$name.err; exit 1; }
+  python3 bench.py --full --no-cpu-baseline --steps 5 $args > $O/$name.json 2> $O/$name.err || { tail -5 $O/$name.err; exit 1; }
 done
 python3 - <<'P'
 import json, glob

@@ -2,8 +2,8 @@
 # one box: the bench kernel time (default layout and separate tables), the box's copy rate, per-XCD streaming rate
 set -o pipefail
 O=gpurun_out/r02/box_$1; mkdir -p $O
-python3 bench.py --no-cpu-baseline --steps 5 > $O/default.json 2> $O/default.err || exit 1
-python3 bench.py --no-cpu-baseline --steps 5 --layout separate_tables > $O/separate.json 2> $O/separate.err || exit 1
+python3 bench.py --full --no-cpu-baseline --steps 5 > $O/default.json 2> $O/default.err || exit 1
+python3 bench.py --full --no-cpu-baseline --steps 5 --layout separate_tables > $O/separate.json 2> $O/separate.err || exit 1
 GE_PROBE_XCD=1 python3 tools/r02/mode_probe.py xcd 3 > $O/xcd.json 2> $O/xcd.err || exit 1
 python3 - $O <<'P'
 import json, sys

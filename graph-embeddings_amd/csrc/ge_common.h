@@ -37,4 +37,7 @@ inline ge_status fail(ge_status code, const char *fmt, ...) {
 // Selects the device and verifies it is gfx950 (there is no fallback path).
 ge_status select_device(int device);
 
+// (focus + context) / 2 of a trainer handle as a device buffer of vocab_size x dim floats (glove.hip; the caller frees it).
+ge_status glove_extract_device_f32(ge_glove *h, float **rows, int32_t *vocab_size, int32_t *dim, int32_t *device);
+
 }  // namespace ge

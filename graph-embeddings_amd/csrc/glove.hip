@@ -1532,10 +1532,10 @@ static ge_status materialize_f32(ge_glove *h, int which, float **out) {
     return GE_OK;
 }
 
-static ge_status extract_impl(ge_glove *h, void *out, bool f64) {
+// (focus + context) / 2 of every row in a fresh device buffer (the caller frees it), enqueued on the handle's stream.
+static ge_status extract_to_device(ge_glove *h, bool f64, void **out) {
     ge_status st = check_handle(h);
     if (st != GE_OK) return st;
-    if (!out) return ge::fail(GE_ERR_ARG, "out is null");
     if (h->rows != h->cfg.vocab_size)
         return ge::fail(GE_ERR_STATE, "extract needs all focus rows on this handle (owned [%d,%d) of %d); gather shards first",
                         h->cfg.row_begin, h->cfg.row_end, h->cfg.vocab_size);
@@ -1554,9 +1554,24 @@ static ge_status extract_impl(ge_glove *h, void *out, bool f64) {
     }
     if (f64) hipLaunchKernelGGL(k_extract<double>, dim3(blocks), dim3(256), 0, h->stream, foc, ctx, (double *)d, n);
     else     hipLaunchKernelGGL(k_extract<float>,  dim3(blocks), dim3(256), 0, h->stream, foc, ctx, (float *)d, n);
+    hipError_t e = hipGetLastError();
+    if (temp) {                                   // the temporaries may go once the kernel that reads them has run
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        (void)hipFree(foc); (void)hipFree(ctx);
+    }
+    if (e != hipSuccess) { (void)hipFree(d); return ge::fail(GE_ERR_HIP, "extract failed: %s", hipGetErrorString(e)); }
+    *out = d;
+    return GE_OK;
+}
+
+static ge_status extract_impl(ge_glove *h, void *out, bool f64) {
+    if (h && !out) return ge::fail(GE_ERR_ARG, "out is null");
+    void *d = nullptr;
+    ge_status st = extract_to_device(h, f64, &d);
+    if (st != GE_OK) return st;
+    const size_t bytes = (size_t)h->cfg.vocab_size * (size_t)h->cfg.dim * (f64 ? sizeof(double) : sizeof(float));
     hipError_t e = hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (temp) { (void)hipFree(foc); (void)hipFree(ctx); }
     (void)hipFree(d);
     if (e != hipSuccess) return ge::fail(GE_ERR_HIP, "extract copy failed: %s", hipGetErrorString(e));
     return GE_OK;
@@ -1746,6 +1761,17 @@ ge_status ge_glove_get_info(ge_glove *h, ge_glove_info *info) {
 
 }  // extern "C"
 namespace ge {
+// What ge_glove_extract_f32 returns, left on the device (pca.hip fits and projects it there): a fresh buffer of V x D floats,
+// complete when this returns; the caller frees it.
+ge_status glove_extract_device_f32(ge_glove *h, float **rows, int32_t *vocab_size, int32_t *dim, int32_t *device) {
+    void *d = nullptr;
+    ge_status st = extract_to_device(h, false, &d);
+    if (st != GE_OK) return st;
+    hipError_t e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) { (void)hipFree(d); return ge::fail(GE_ERR_HIP, "extract failed: %s", hipGetErrorString(e)); }
+    *rows = (float *)d; *vocab_size = h->cfg.vocab_size; *dim = h->cfg.dim; *device = h->cfg.device;
+    return GE_OK;
+}
 // A Hogwild epoch in `nseg` launches (ge_sync_epoch: the hub rows of a sharded run are reconciled between them).  The chunks of
 // the epoch are handed out by ticket through a keyed bijection, so tickets [n seg / nseg, n (seg + 1) / nseg) are a random nseg-th
 // of the epoch; the cost accumulates on the device over the segments.  Nothing here blocks the host: glove_epoch_finish does.

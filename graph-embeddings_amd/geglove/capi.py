@@ -35,6 +35,8 @@ SYMBOLS = (
     "ge_local_group_create", "ge_local_group_destroy", "ge_local_group_abort", "ge_rccl_unique_id", "ge_rccl_selftest", "ge_sync_cfg_size", "ge_sync_create", "ge_sync_begin", "ge_sync_finish", "ge_sync_turn", "ge_sync_sync",
     "ge_sync_epoch", "ge_sync_hub_rows", "ge_sync_hub_exchange", "ge_sync_hub_exchange_live", "ge_sync_live_rows", "ge_sync_hub_plan", "ge_sync_replicate", "ge_sync_allreduce_f64", "ge_sync_destroy",
     "ge_sim_cfg_default", "ge_sim_cfg_size", "ge_sim_pattern_supported", "ge_similarity_pairs", "ge_sim_pairs_get", "ge_sim_pairs_destroy", "ge_copy_bandwidth", "ge_last_error", "ge_version", "ge_glove_cfg_size", "ge_bca_cfg_size", "ge_device_count",
+    "ge_pca_cfg_default", "ge_pca_cfg_size", "ge_pca_fit", "ge_glove_pca_fit", "ge_pca_from_moments", "ge_pca_get", "ge_pca_transform",
+    "ge_glove_pca_transform", "ge_pca_last_kernel_ms", "ge_pca_destroy",
 )
 
 
@@ -98,6 +100,10 @@ class Transport(C.Structure):
 class SyncCfg(C.Structure):
     _fields_ = [("world", C.c_int32), ("rank", C.c_int32), ("wire", C.c_int32), ("accum_every", C.c_int32),
                 ("transport", C.POINTER(Transport)), ("rccl_id", C.c_void_p), ("local_group", C.c_void_p)]
+
+
+class PcaCfg(C.Structure):
+    _fields_ = [("variance", C.c_double), ("max_components", C.c_int32), ("device", C.c_int32), ("stream", C.c_void_p)]
 
 
 class GeError(RuntimeError):
@@ -201,12 +207,116 @@ def lib():
     if L.ge_glove_cfg_size() != C.sizeof(GloveCfg):
         raise ImportError("libgeglove.so was built from another revision of include/geglove.h (ge_glove_cfg is %d bytes there, "
                           "%d here): rebuild with `make -C graph-embeddings_amd/csrc`" % (L.ge_glove_cfg_size(), C.sizeof(GloveCfg)))
+    _declare_pca(L)
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int:      # default restype -> ge_status
             f.restype = C.c_int32
     _lib = L
     return L
+
+
+def _declare_pca(L):
+    """The PCA section of include/geglove.h."""
+    vp, f32p, f64p = C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_double)
+    L.ge_pca_cfg_default.argtypes = [C.POINTER(PcaCfg)]; L.ge_pca_cfg_default.restype = None
+    L.ge_pca_cfg_size.argtypes = []; L.ge_pca_cfg_size.restype = C.c_int32
+    if L.ge_pca_cfg_size() != C.sizeof(PcaCfg):
+        raise ImportError("libgeglove.so was built from another revision of include/geglove.h (ge_pca_cfg is %d bytes there, %d here): "
+                          "rebuild with `make -C graph-embeddings_amd/csrc`" % (L.ge_pca_cfg_size(), C.sizeof(PcaCfg)))
+    L.ge_pca_fit.argtypes = [f32p, C.c_int64, C.c_int32, C.POINTER(PcaCfg), C.POINTER(vp)]
+    L.ge_glove_pca_fit.argtypes = [vp, C.POINTER(PcaCfg), C.POINTER(vp)]
+    L.ge_pca_from_moments.argtypes = [f64p, f64p, C.c_int32, C.c_int64, C.POINTER(PcaCfg), C.POINTER(vp)]
+    L.ge_pca_get.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(f64p), C.POINTER(f64p),
+                             C.POINTER(f64p), C.POINTER(f64p)]
+    L.ge_pca_transform.argtypes = [vp, f32p, C.c_int64, f32p]
+    L.ge_glove_pca_transform.argtypes = [vp, vp, f32p]
+    L.ge_pca_last_kernel_ms.argtypes = [vp, f32p, f32p]
+    L.ge_pca_destroy.argtypes = [vp]; L.ge_pca_destroy.restype = None
+
+
+class Pca:
+    """A ge_pca model: Pca.fit(rows) / Pca.fit_glove(handle) / Pca.from_moments(mean, cov, n_rows), then the tables of
+    ge_pca_get as numpy arrays (copies) and transform(rows) / transform_glove(handle)."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @staticmethod
+    def _cfg(variance, max_components, device):
+        cfg = PcaCfg(); lib().ge_pca_cfg_default(C.byref(cfg))
+        cfg.variance, cfg.max_components, cfg.device = variance, max_components, device
+        return cfg
+
+    @classmethod
+    def fit(cls, rows, variance=0.95, max_components=0, device=0):
+        import numpy as np
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        h = C.c_void_p()
+        check(lib().ge_pca_fit(rows.ctypes.data_as(C.POINTER(C.c_float)), rows.shape[0], rows.shape[1],
+                               C.byref(cls._cfg(variance, max_components, device)), C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def fit_glove(cls, glove_handle, variance=0.95, max_components=0):
+        h = C.c_void_p()
+        check(lib().ge_glove_pca_fit(glove_handle, C.byref(cls._cfg(variance, max_components, 0)), C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def from_moments(cls, mean, cov, n_rows, variance=0.95, max_components=0, device=0):
+        import numpy as np
+        mean = np.ascontiguousarray(mean, dtype=np.float64); cov = np.ascontiguousarray(cov, dtype=np.float64)
+        f64p = C.POINTER(C.c_double)
+        h = C.c_void_p()
+        check(lib().ge_pca_from_moments(mean.ctypes.data_as(f64p), cov.ctypes.data_as(f64p), mean.shape[0], n_rows,
+                                        C.byref(cls._cfg(variance, max_components, device)), C.byref(h)))
+        return cls(h)
+
+    def get(self):
+        """(dim, k, n_rows, mean[dim], cov[dim, dim], eigenvalues[dim], components[dim, dim]); column c of components is the
+        unit eigenvector of the c-th largest eigenvalue."""
+        import numpy as np
+        f64p = C.POINTER(C.c_double)
+        dim, k, n = C.c_int32(), C.c_int32(), C.c_int64()
+        mean, cov, eig, comp = f64p(), f64p(), f64p(), f64p()
+        check(lib().ge_pca_get(self._h, C.byref(dim), C.byref(k), C.byref(n), C.byref(mean), C.byref(cov), C.byref(eig), C.byref(comp)))
+        D = dim.value
+        arr = lambda p, shape: np.ctypeslib.as_array(p, shape=shape).copy()
+        return D, k.value, n.value, arr(mean, (D,)), arr(cov, (D, D)), arr(eig, (D,)), arr(comp, (D, D))
+
+    @property
+    def k(self):
+        return self.get()[1]
+
+    def transform(self, rows):
+        import numpy as np
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        out = np.empty((rows.shape[0], self.k), dtype=np.float32)
+        check(lib().ge_pca_transform(self._h, rows.ctypes.data_as(C.POINTER(C.c_float)), rows.shape[0], out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def transform_glove(self, glove_handle, vocab_size):
+        import numpy as np
+        out = np.empty((vocab_size, self.k), dtype=np.float32)
+        check(lib().ge_glove_pca_transform(self._h, glove_handle, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def kernel_ms(self):
+        fit, tr = C.c_float(), C.c_float()
+        check(lib().ge_pca_last_kernel_ms(self._h, C.byref(fit), C.byref(tr)))
+        return fit.value, tr.value
+
+    def close(self):
+        if self._h:
+            lib().ge_pca_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def check(status):

@@ -255,7 +255,9 @@ struct Configuration {
              double hot_theta = 0, stale_budget = 0; int flush_every = 0, blocks_per_cu = 0, layout_flags = 0;
              long long bca_table_slots = 0, bca_pool_entries = 0;
              // multi-GPU: gpus ranks, one thread each, rows sharded, context exchanged through ge_sync
-             int gpus = 1, accum_every = 0, hub_segments = 0; std::string exchange = "overlap", transport = "auto", wire = "bf16"; } device;
+             int gpus = 1, accum_every = 0, hub_segments = 0; std::string exchange = "overlap", transport = "auto", wire = "bf16";
+             // off | apply: reduce the trained vectors to the leading components the `pca:` block asks for before they are written
+             std::string pca = "off"; } device;
     std::vector<std::string> ignored_keys;     // legacy keys of the shipped YAMLs that the bean does not know
 
     int getThreads() const {       // Configuration.java:71-73
@@ -265,6 +267,7 @@ struct Configuration {
     }
     std::string getNormalize() const { return bca.normalize.empty() ? "none" : bca.normalize; }
     bool usingPca() const { return pca.present; }
+    bool applyingPca() const { return device.pca == "apply"; }
     bool usingWeights() const { return has_weights && !weights.empty(); }
     bool usingSimilarity() const { return !similarity.empty(); }
 
@@ -343,6 +346,7 @@ struct Configuration {
                     else if (q.first == "save_coo") c.device.save_coo = q.second.scalar;      // COO checkpoint
                     else if (q.first == "load_coo") c.device.load_coo = q.second.scalar;
                     else if (q.first == "gpus") c.device.gpus = std::max(1, (int)num(&q.second));
+                    else if (q.first == "pca") c.device.pca = q.second.scalar;
                     else if (q.first == "exchange") c.device.exchange = q.second.scalar;        // overlap | sync
                     else if (q.first == "transport") c.device.transport = q.second.scalar;      // auto | rccl | host
                     else if (q.first == "wire") c.device.wire = q.second.scalar;                // bf16 | f32
@@ -380,6 +384,9 @@ struct Configuration {
         if (c.method.empty()) throw InvalidConfigurationException("Invalid method, choose one of: glove, pglove");
         if (!hasBca) throw InvalidConfigurationException("Invalid BCA parameters, alpha and epsilon are mandatory");
         if (!hasOut) throw InvalidConfigurationException("Invalid output parameters, specify at least one group");
+        if (c.device.pca != "off" && c.device.pca != "apply") throw InvalidConfigurationException("Invalid device.pca, choose one of: off, apply");
+        if (c.applyingPca() && !c.usingPca()) throw InvalidConfigurationException("device.pca: apply needs a pca block with a variance");
+        if (c.applyingPca() && !(c.pca.variance > 0 && c.pca.variance <= 1)) throw InvalidConfigurationException("Invalid PCA parameters, variance must lie in (0, 1]");
     }
 
     static std::string similarity_to_string(const std::map<std::string, std::string> &m) {     // SimilarityGroup.toString
@@ -1099,6 +1106,37 @@ inline std::unique_ptr<IOptimizer> createOptimizer(const Configuration &config, 
     throw std::invalid_argument("Invalid optimization method");
 }
 
+// `device: { pca: apply }`: the stage the reference announces and never runs (it prints "PCA Minimum Variance" and writes the full
+// vectors).  Fits on all V rows of the result -- on device.id, once, also after a multi-GPU run (the result is replicated) -- and
+// replaces it by the V x k projection; returns the line Main logs.
+inline std::string applyPca(const Configuration &config, Optimum &optimum, int V) {
+    if (ge_pca_cfg_size() != (int32_t)sizeof(ge_pca_cfg))
+        throw std::runtime_error("libgeglove.so and this host were built from different revisions of include/geglove.h; rebuild both");
+    if (V < 1 || optimum.result.size() % (size_t)V != 0) throw std::runtime_error("PCA: the result is not a table of V rows");
+    const int D = (int)(optimum.result.size() / (size_t)V);
+    std::vector<float> rows(optimum.result.begin(), optimum.result.end());      // widened fp32 values: exact
+    ge_pca_cfg cfg;
+    ge_pca_cfg_default(&cfg);
+    cfg.variance = config.pca.variance;
+    cfg.device = config.device.id;
+    ge_pca *raw = nullptr;
+    check(ge_pca_fit(rows.data(), V, D, &cfg, &raw));
+    struct Del { void operator()(ge_pca *p) const { ge_pca_destroy(p); } };
+    std::unique_ptr<ge_pca, Del> model(raw);
+    int32_t k = 0;
+    const double *lambda = nullptr;
+    check(ge_pca_get(model.get(), nullptr, &k, nullptr, nullptr, nullptr, &lambda, nullptr));
+    std::vector<float> out((size_t)V * (size_t)k);
+    check(ge_pca_transform(model.get(), rows.data(), V, out.data()));
+    double total = 0, kept = 0;
+    for (int c = 0; c < D; ++c) { total += lambda[c]; if (c < k) kept += lambda[c]; }
+    optimum.result.assign(out.begin(), out.end());
+    char b[200];
+    std::snprintf(b, sizeof b, "kept %d of %d components (%.6f of the variance >= %s)", (int)k, D, total > 0 ? kept / total : 0.0,
+                  java_number(config.pca.variance, false).c_str());
+    return b;
+}
+
 // ------------------------------------------------------------------------------------------------
 // EmbeddingTextWriter (J/util/write/EmbeddingTextWriter.java)
 // ------------------------------------------------------------------------------------------------
@@ -1115,7 +1153,8 @@ public:
         if (!dict || !vect) throw std::runtime_error("cannot open output files in " + outputFolder);
         for (auto &l : config_.banner()) { dict << "# " << l << "\n"; vect << "# " << l << "\n"; }
         dict << "key\ttype\n";
-        const int V = m.vocabSize(), D = config_.dim;
+        const int V = m.vocabSize();
+        const int D = V > 0 ? (int)(optimum.result.size() / (size_t)V) : config_.dim;     // config.dim, or the k columns `device.pca: apply` left
         static const char *names[3] = {"URI", "BLANK", "LITERAL"};
         long long written = 0;
         // which vertices are written (type switch, then the prefix filter of that type: EmbeddingTextWriter.java:100-131), in order

@@ -62,12 +62,13 @@ static void runProgram(const Configuration &config) {                       // J
     }
     g_tolerance = config.opt.tolerance;
     std::unique_ptr<IOptimizer> optimizer = createOptimizer(config, bca, progress);
-    const Optimum optimum = optimizer->optimize();
+    Optimum optimum = optimizer->optimize();
     {
         char b[120];
         std::snprintf(b, sizeof b, "Finished optimization with final cost: %.12g", optimum.finalCost);
         log_info("Optimizer", b);
     }
+    if (config.applyingPca()) log_info("PCA", applyPca(config, optimum, bca.vocabSize()));
     EmbeddingTextWriter writer(outFileName, config);
     const long long n = writer.write(optimum, bca, "out");
     log_info("EmbeddingTextWriter", "wrote " + std::to_string(n) + " vectors to out/" + writer.vectorsFile());

@@ -485,6 +485,54 @@ ge_status ge_sync_replicate(ge_sync *s, int32_t src);
 ge_status ge_sync_allreduce_f64(ge_sync *s, double *values, int32_t n, int32_t op);
 void ge_sync_destroy(ge_sync *s);
 
+/* ------------------------------------------------------------------------------------------
+ * PCA of the trained vectors (the `pca: { variance }` block of the shipped YAMLs).  The reference parses that block and
+ * prints it (J/Main.java:43-44) but never reduces anything, so these are product semantics:
+ *   moments   mean[d] = sum_r x[r][d] / n,  cov[a][b] = sum_r (x[r][a] - mean[a]) (x[r][b] - mean[b]) / (n - 1), accumulated
+ *             in fp64 on the device (k_pca_gram, fp64 matrix cores); a fixed partition of the rows and a fixed-order
+ *             reduction, no floating-point atomics: the same input on the same device gives the same bytes, call after call.
+ *             Non-finite moments are GE_ERR_ARG ("non-finite input").
+ *   model     eigen-decomposition of cov on the host in fp64 (Householder tridiagonalisation + implicit QL, own code).
+ *             Eigenvalues descending, negative rounding residue clamped to 0; in every component the entry of largest
+ *             magnitude is positive (lowest index on a tie).
+ *   k         the smallest k >= 1 with  sum_{c<k} lambda_c >= variance * sum_c lambda_c  (fp64, in that order), then capped
+ *             by max_components.  Constant input (sum lambda = 0): k = 1 and a projection of zeros.
+ *   transform out[r][c] = sum_d (x[r][d] - mean[d]) * components[d][c]: centred first (in fp64, rounded to fp32 once), then
+ *             the products in fp32 in ascending d (k_pca_project, an fmaf chain on the fp32 matrix cores).
+ * Limits: 2 <= n_rows, 1 <= dim <= 1024, variance in (0, 1], max_components >= 0; anything else is GE_ERR_ARG, checked
+ * before any device work.  No device: GE_ERR_HIP.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct ge_pca ge_pca;
+typedef struct {
+    double  variance;        /* pca.variance: keep the fewest leading components whose eigenvalues sum to >= variance * total */
+    int32_t max_components;  /* > 0: never keep more than this many; 0 = no cap */
+    int32_t device;          /* HIP device ordinal */
+    void   *stream;          /* hipStream_t or NULL */
+} ge_pca_cfg;
+void      ge_pca_cfg_default(ge_pca_cfg *cfg);            /* variance 0.95, no cap, device 0 */
+int32_t   ge_pca_cfg_size(void);
+
+/* rows: HOST float[n_rows * dim], row-major; uploaded in slabs (no second copy of the table on either side). */
+ge_status ge_pca_fit(const float *rows, int64_t n_rows, int32_t dim, const ge_pca_cfg *cfg, ge_pca **out);
+/* The same on the vectors a trainer handle holds -- (focus + context) / 2, what ge_glove_extract_f32 returns -- without the
+ * trip through host memory; bit for bit the model ge_pca_fit builds from that output.  Runs on the handle's device. */
+ge_status ge_glove_pca_fit(ge_glove *h, const ge_pca_cfg *cfg, ge_pca **out);
+/* HOST ONLY, needs no device: the model from moments a caller already has (a sharded run sums its shards' moments).
+ * mean[dim], cov[dim*dim] symmetric, the covariance with divisor n_rows - 1. */
+ge_status ge_pca_from_moments(const double *mean, const double *cov, int32_t dim, int64_t n_rows,
+                              const ge_pca_cfg *cfg, ge_pca **out);
+/* Host views, valid until ge_pca_destroy; any out pointer may be NULL.  components: double[dim*dim], column c (element
+ * [d*dim + c]) is the unit eigenvector of the c-th LARGEST eigenvalue; eigenvalues: double[dim] descending; *k = kept. */
+ge_status ge_pca_get(const ge_pca *p, int32_t *dim, int32_t *k, int64_t *n_rows, const double **mean, const double **cov,
+                     const double **eigenvalues, const double **components);
+/* out: HOST float[n_rows * k] */
+ge_status ge_pca_transform(const ge_pca *p, const float *rows, int64_t n_rows, float *out);
+ge_status ge_glove_pca_transform(const ge_pca *p, ge_glove *h, float *out);     /* out: HOST float[V * k] */
+/* Device time of the handle's last moment pass (ge_pca_fit, ge_glove_pca_fit) and last projection, hipEvents around the
+ * kernels, in milliseconds (0 = none ran); uploads are not counted.  Either out pointer may be NULL. */
+ge_status ge_pca_last_kernel_ms(const ge_pca *p, float *fit_ms, float *transform_ms);
+void      ge_pca_destroy(ge_pca *p);
+
 /* ------------------------------------------------------------------------------------------ */
 const char *ge_last_error(void);     /* message of the calling thread's last failed call */
 const char *ge_version(void);

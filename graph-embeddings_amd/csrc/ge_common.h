@@ -27,6 +27,9 @@ inline ge_status fail(ge_status code, const char *fmt, ...) {
                             __FILE__, __LINE__);                                         \
     } while (0)
 
+// a step that returns a ge_status (and has left its message with ge::fail): pass a failure on
+#define GE_CHECK(expr) do { ge_status _s = (expr); if (_s != GE_OK) return _s; } while (0)
+
 // No C++ exception crosses the C ABI: entry points whose bodies allocate on the host run as  GE_GUARD(name_impl(args)).
 #define GE_GUARD(call)                                                                                     \
     try { return (call); }                                                                                  \
@@ -36,8 +39,5 @@ inline ge_status fail(ge_status code, const char *fmt, ...) {
 
 // Selects the device and verifies it is gfx950 (there is no fallback path).
 ge_status select_device(int device);
-
-// (focus + context) / 2 of a trainer handle as a device buffer of vocab_size x dim floats (glove.hip; the caller frees it).
-ge_status glove_extract_device_f32(ge_glove *h, float **rows, int32_t *vocab_size, int32_t *dim, int32_t *device);
 
 }  // namespace ge

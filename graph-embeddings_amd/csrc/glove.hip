@@ -14,6 +14,7 @@
 // run (ge_glove_info.schedule_bytes).  No MFMA: sparse gather + length-D dot.
 
 #include "ge_common.h"
+#include "ge_glove_internal.h"
 #include "ge_javarand.h"
 #include "ge_cost.h"
 #include "ge_layout.h"
@@ -23,6 +24,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <chrono>
+#include <memory>
 #include <new>
 #include <type_traits>
 #include <vector>
@@ -171,18 +173,13 @@ __global__ void k_extract(const float *focus, const float *context, OUT *out, in
 
 // Fat rows (fp32 Hogwild tables): [row(D) | bias | 3 x 0].  Columns [col0, col0+ncols) of `rows` fat rows <-> a dense
 // [rows x ncols] array: ncols = D, col0 = 0 is the row table as the API shows it, ncols = 1, col0 = D its bias vector.
-__global__ void k_fat_gather(const float *fat, int64_t rows, int32_t DS, int32_t col0, int32_t ncols, float *dense) {
+template <bool TO_DENSE>
+__global__ void k_fat_copy(float *fat, int64_t rows, int32_t DS, int32_t col0, int32_t ncols, float *dense) {
     const int64_t n = rows * ncols, stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const int64_t r = i / ncols; const int32_t c = (int32_t)(i - r * ncols);
-        dense[i] = fat[r * DS + col0 + c];
-    }
-}
-__global__ void k_fat_scatter(float *fat, int64_t rows, int32_t DS, int32_t col0, int32_t ncols, const float *dense) {
-    const int64_t n = rows * ncols, stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const int64_t r = i / ncols; const int32_t c = (int32_t)(i - r * ncols);
-        fat[r * DS + col0 + c] = dense[i];
+        if constexpr (TO_DENSE) dense[i] = fat[r * DS + col0 + c];
+        else fat[r * DS + col0 + c] = dense[i];
     }
 }
 
@@ -192,8 +189,8 @@ __global__ void k_f32_to_bf16(const float *src, uint16_t *dst, int64_t n, int32_
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (; i < n; i += stride) {
-        const uint32_t u = __builtin_bit_cast(uint32_t, src[i]);
-        const int64_t r = i / D;
+        const uint32_t u = __builtin_bit_cast(uint32_t, src[i]);       // bf16_rne, restated: calling it here makes the compiler unroll
+        const int64_t r = i / D;                                        // this loop (216 -> 784 instructions for the same result)
         dst[r * es + (i - r * D)] = (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
     }
 }
@@ -937,44 +934,34 @@ __global__ __launch_bounds__(256) void k_probe_records(float *tab, int64_t rows,
 
 using hogwild_fn = void (*)(GloveParams, int32_t);
 
-
-template <int VW, int OPT, bool FAT>
+// One wavefront spans a row: 64 lanes x VW floats x NCH chunks >= D.  A row carries its bias at element [D] (fat rows; bf16 rows:
+// behind the accumulator row) when the lane that would hold it lies in the row's last 64-lane chunk.  An odd dim, or twice an odd
+// number, never fills its 64-lane chunks, so VW 1 and VW 2 exist with fat rows only.
+struct HogwildKernel { hogwild_fn fn; int vw, nch; bool fat; };
+template <int VW, int OPT, bool BF16, bool FAT>
 hogwild_fn pick_nch(int nch) {
+    static_assert(VW == 4 || FAT, "no dim reaches VW < 4 without fat rows");
     switch (nch) {
-        case 1: return k_adagrad_runs<VW, 1, OPT, false, FAT>;
-        case 2: return k_adagrad_runs<VW, 2, OPT, false, FAT>;
-        case 3: return k_adagrad_runs<VW, 3, OPT, false, FAT>;
-        case 4: return k_adagrad_runs<VW, 4, OPT, false, FAT>;
+        case 1: return k_adagrad_runs<VW, 1, OPT, BF16, FAT>;
+        case 2: return k_adagrad_runs<VW, 2, OPT, BF16, FAT>;
+        case 3: return k_adagrad_runs<VW, 3, OPT, BF16, FAT>;
+        case 4: return k_adagrad_runs<VW, 4, OPT, BF16, FAT>;
         default: return nullptr;
     }
 }
-template <bool FAT>
-hogwild_fn pick_bf16(int nch) {       // bf16 embeddings: AdaGrad, dim % 4 == 0
-    switch (nch) {
-        case 1: return k_adagrad_runs<4, 1, GE_OPT_ADAGRAD, true, FAT>;
-        case 2: return k_adagrad_runs<4, 2, GE_OPT_ADAGRAD, true, FAT>;
-        case 3: return k_adagrad_runs<4, 3, GE_OPT_ADAGRAD, true, FAT>;
-        case 4: return k_adagrad_runs<4, 4, GE_OPT_ADAGRAD, true, FAT>;
-        default: return nullptr;
-    }
-}
-template <int OPT, bool FAT>
-hogwild_fn pick_vw(int vw, int nch) { return vw == 4 ? pick_nch<4, OPT, FAT>(nch) : vw == 2 ? pick_nch<2, OPT, FAT>(nch) : pick_nch<1, OPT, FAT>(nch); }
 template <int OPT>
-hogwild_fn pick_fat(int vw, int nch, bool fat) { return fat ? pick_vw<OPT, true>(vw, nch) : pick_vw<OPT, false>(vw, nch); }
-// rows carry their bias at element [D] (fat rows; bf16 rows: behind the accumulator row) when the lane that would hold it lies in
-// the row's last 64-lane chunk
-inline bool fat_rows_fit(int D) { const int vw = (D % 4 == 0) ? 4 : (D % 2 == 0) ? 2 : 1; return ((D / vw) % 64) != 0; }
-// One wavefront spans a row: 64 lanes x VW floats x NCH chunks >= D.
-hogwild_fn pick_hogwild(int D, int opt, bool emb16, int *vw_out, int *nch_out) {
+hogwild_fn pick_f32(int vw, int nch, bool fat) {
+    if (!fat) return pick_nch<4, OPT, false, false>(nch);
+    return vw == 4 ? pick_nch<4, OPT, false, true>(nch) : vw == 2 ? pick_nch<2, OPT, false, true>(nch) : pick_nch<1, OPT, false, true>(nch);
+}
+HogwildKernel pick_hogwild(int D, int opt, bool emb16) {
     const int vw = (D % 4 == 0) ? 4 : (D % 2 == 0) ? 2 : 1;
-    const bool fat = fat_rows_fit(D);
+    const bool fat = ((D / vw) % 64) != 0;                   // false only with vw == 4: D is then a multiple of 64 vw
     const int nch = (D + 64 * vw - 1) / (64 * vw);           // the bias lane of a fat row lies inside the last chunk
-    hogwild_fn fn = emb16 ? (fat ? pick_bf16<true>(nch) : pick_bf16<false>(nch))
-                  : opt == GE_OPT_ADAGRAD ? pick_fat<GE_OPT_ADAGRAD>(vw, nch, fat)
-                  : opt == GE_OPT_ADAM ? pick_fat<GE_OPT_ADAM>(vw, nch, fat) : pick_fat<GE_OPT_AMSGRAD>(vw, nch, fat);
-    *vw_out = vw; *nch_out = nch;
-    return fn;
+    hogwild_fn fn = emb16 ? (fat ? pick_nch<4, GE_OPT_ADAGRAD, true, true>(nch) : pick_nch<4, GE_OPT_ADAGRAD, true, false>(nch))   // bf16 embeddings: AdaGrad, dim % 4 == 0
+                  : opt == GE_OPT_ADAGRAD ? pick_f32<GE_OPT_ADAGRAD>(vw, nch, fat)
+                  : opt == GE_OPT_ADAM ? pick_f32<GE_OPT_ADAM>(vw, nch, fat) : pick_f32<GE_OPT_AMSGRAD>(vw, nch, fat);
+    return {fn, vw, nch, fat};
 }
 
 }  // namespace
@@ -1001,8 +988,7 @@ struct ge_glove {
     float last_ms = 0.0f;
     int32_t last_launches = 0;
     int num_cus = 256;
-    hogwild_fn hw_fn = nullptr;
-    int hw_vw = 0, hw_nch = 0;
+    HogwildKernel hw{};               // Hogwild: the kernel instance and its lane shape (pick_hogwild)
     int hw_blocks_per_cu = 4;
     int hw_blocks = 0;
     int hw_workers = 0;
@@ -1011,9 +997,10 @@ struct ge_glove {
     int64_t n_chunks = 0, n_hchunks = 0;
     int flush_every = RUN_CHUNK;
     bool emb16 = false;               // focus/context stored as bf16 (tab[] pointers then address uint16 data)
-    bool fat = false;                 // fp32 Hogwild: a row is D + 4 floats with its bias at [D]; tab[*BIAS] are null
+    bool fat = false;                 // Hogwild: a row is D + 4 floats with its bias at [D] (pick_hogwild); tab[*BIAS] are null
     int32_t rw = 0;                   // row width of the fp32 row tables in floats (D, or D + 4 when fat)
     int32_t ds = 0;                   // row stride of the fp32 row tables in floats (rw, or a multiple when the tables interleave)
+    int32_t e16 = 0;                  // bf16 rows: bf16 elements of a row padded to 16 bytes (what leads a record)
     int32_t es = 0;                   // bf16 rows: bf16 elements between consecutive embedding rows (dim, or 2 * ds inside records)
     int32_t placements = 0;           // allocations tried for the record tables (both sides)
     float place_best_ms = 0.0f, place_worst_ms = 0.0f;
@@ -1028,6 +1015,9 @@ struct ge_glove {
     int32_t hot_cols = 0;
     int64_t hot_nnz = 0, hot_threshold = 0;
 
+    bool hogwild() const { return cfg.mode == GE_MODE_HOGWILD; }
+    bool moments() const { return cfg.opt != GE_OPT_ADAGRAD; }      // Adam / AMSGrad keep M2* next to M1*
+    bool interleaved() const { return hogwild() && (cfg.layout_flags & GE_LAYOUT_SEPARATE_TABLES) == 0; }   // a side is one table of records
     template <typename T> hipError_t alloc(T **out, size_t n) {
         hipError_t e = hipMalloc((void **)out, sizeof(T) * std::max<size_t>(n, 1));
         if (e == hipSuccess) owned.push_back((void *)*out);
@@ -1042,6 +1032,38 @@ ge_status check_handle(ge_glove *h) {
     hipError_t e = hipSetDevice(h->cfg.device);
     if (e != hipSuccess) return ge::fail(GE_ERR_HIP, "hipSetDevice(%d): %s", h->cfg.device, hipGetErrorString(e));
     return GE_OK;
+}
+ge_status hip_failed(const char *what, hipError_t e) { return ge::fail(GE_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e)); }
+
+// a device buffer that lives as long as its scope (staging copies of the accessors), unless released to the caller
+struct DeviceBuf {
+    void *p = nullptr;
+    DeviceBuf() = default;
+    DeviceBuf(const DeviceBuf &) = delete;
+    DeviceBuf &operator=(const DeviceBuf &) = delete;
+    ~DeviceBuf() { if (p) (void)hipFree(p); }
+    float *f32() const { return static_cast<float *>(p); }
+    void *release() { void *q = p; p = nullptr; return q; }
+};
+
+// The keyed bijection (bij_round) permutes [0, 2^bits), the smallest power of two that covers `domain`.
+void bijection_width(int64_t domain, uint32_t *mask, uint32_t *shift) {
+    uint32_t bits = 0;
+    while (bits < 31 && ((int64_t)1 << bits) < domain) ++bits;
+    *mask = bits >= 32 ? 0xFFFFFFFFu : ((1u << bits) - 1u);
+    *shift = bits > 1 ? bits / 2 : 1;
+}
+// SplitMix64 of (seed, iteration) -> four round keys
+void bijection_keys(int64_t seed, int32_t iteration, uint32_t key[4]) {
+    uint64_t z = (uint64_t)seed * 0x9E3779B97F4A7C15ULL + (uint64_t)(uint32_t)iteration * 0xD1B54A32D192ED03ULL + 0x632BE59BD9B4E019ULL;
+    for (int q = 0; q < 4; ++q) {
+        z += 0x9E3779B97F4A7C15ULL;
+        uint64_t t = z;
+        t = (t ^ (t >> 30)) * 0xBF58476D1CE4E5B9ULL;
+        t = (t ^ (t >> 27)) * 0x94D049BB133111EBULL;
+        t ^= t >> 31;
+        key[q] = (uint32_t)t;
+    }
 }
 
 void fill_params(const ge_glove *h, GloveParams &p, int32_t iteration) {
@@ -1076,62 +1098,145 @@ void fill_params(const ge_glove *h, GloveParams &p, int32_t iteration) {
     p.bA = h->lay.bA; p.bB = h->lay.bB; p.cstart = h->lay.cstart; p.cmeta = h->lay.cmeta; p.n_chunks = h->n_chunks; p.n_hchunks = h->n_hchunks;
     p.ticket_end = h->n_chunks;
     p.blocked = h->blocked ? 1 : 0; p.hot_enabled = h->cfg.hot_columns != GE_HOT_NONE; p.flush_every = h->flush_every;
-    const int64_t domain = h->blocked ? h->n_chunks : h->cfg.nnz;      // what the keyed bijection permutes
-    uint32_t bits = 0;
-    while (bits < 31 && ((int64_t)1 << bits) < domain) ++bits;
-    p.bij_mask = bits >= 32 ? 0xFFFFFFFFu : ((1u << bits) - 1u);
-    p.bij_shift = bits > 1 ? bits / 2 : 1;
-    // SplitMix64 of (seed, iteration) -> four round keys
-    uint64_t z = (uint64_t)h->cfg.seed * 0x9E3779B97F4A7C15ULL + (uint64_t)(uint32_t)iteration * 0xD1B54A32D192ED03ULL + 0x632BE59BD9B4E019ULL;
-    for (int q = 0; q < 4; ++q) {
-        z += 0x9E3779B97F4A7C15ULL;
-        uint64_t t = z;
-        t = (t ^ (t >> 30)) * 0xBF58476D1CE4E5B9ULL;
-        t = (t ^ (t >> 27)) * 0x94D049BB133111EBULL;
-        t ^= t >> 31;
-        p.bij_key[q] = (uint32_t)t;
-    }
+    bijection_width(h->blocked ? h->n_chunks : h->cfg.nnz, &p.bij_mask, &p.bij_shift);      // what the keyed bijection permutes
+    bijection_keys(h->cfg.seed, iteration, p.bij_key);
 }
 
-}  // namespace
-
-extern "C" {
-
-void ge_glove_cfg_default(ge_glove_cfg *cfg) {
-    if (!cfg) return;
-    std::memset(cfg, 0, sizeof(*cfg));
-    cfg->cost = GE_COST_GLOVE;
-    cfg->opt = GE_OPT_ADAGRAD;
-    cfg->learning_rate = 0.05f;
-    cfg->threads = 1;
-    cfg->mode = GE_MODE_HOGWILD;
-    cfg->shuffle = GE_SHUFFLE_DEVICE;
-}
-
-// Where the API's table `which` lives on the device.  Fat handles keep no bias tables: an fp32 row carries its bias at column
-// [dim] (and the accumulator / moment row the bias's accumulator / moment there); a bf16 handle's rows cannot, so both scalars sit
-// behind the ACCUMULATOR row: [gradSq (dim) | the bias accumulator | the bias | 2 x 0].
-static const int FAT_HOME[GE_STATE_COUNT] = {GE_STATE_FOCUS, GE_STATE_CONTEXT, GE_STATE_FOCUS, GE_STATE_CONTEXT,
-                                             GE_STATE_GSQ_FOCUS, GE_STATE_GSQ_CONTEXT, GE_STATE_GSQ_FOCUS, GE_STATE_GSQ_CONTEXT,
-                                             GE_STATE_M2_FOCUS, GE_STATE_M2_CONTEXT, GE_STATE_M2_FOCUS, GE_STATE_M2_CONTEXT};
-static bool is_bias_table(int which) { return FAT_HOME[which] != which; }
-struct Home { float *base; int32_t col0, ncols; int64_t stride; };       // table[r][c] = base[r * stride + col0 + c], c < ncols
-static Home home_of(const ge_glove *h, int which) {
+// Where the API's table `which` lives on the device and what it looks like there: table[r][c] = base[r * stride + col0 + c], c < ncols.
+// Fat handles keep no bias tables: an fp32 row carries its bias at column [dim] (and the accumulator / moment row the bias's
+// accumulator / moment there); a bf16 handle's rows cannot, so both scalars sit behind the ACCUMULATOR row:
+// [gradSq (dim) | the bias accumulator | the bias | 2 x 0].  bf16: FOCUS / CONTEXT of a bf16 handle, `base` then addresses uint16
+// elements and `stride` counts them (the hub columns of CONTEXT also have fp32 master rows in hub32).
+const int FAT_HOME[GE_STATE_COUNT] = {GE_STATE_FOCUS, GE_STATE_CONTEXT, GE_STATE_FOCUS, GE_STATE_CONTEXT,
+                                      GE_STATE_GSQ_FOCUS, GE_STATE_GSQ_CONTEXT, GE_STATE_GSQ_FOCUS, GE_STATE_GSQ_CONTEXT,
+                                      GE_STATE_M2_FOCUS, GE_STATE_M2_CONTEXT, GE_STATE_M2_FOCUS, GE_STATE_M2_CONTEXT};
+bool is_bias_table(int which) { return FAT_HOME[which] != which; }
+struct TableView {
+    float *base; int32_t col0, ncols; int64_t stride; bool bf16;
+    bool dense() const { return !bf16 && stride == ncols; }              // the API's view is the stored bytes
+    float *first() const { return base ? base + col0 : nullptr; }         // table[0][0] (fp32 views)
+};
+TableView view_of(const ge_glove *h, int which) {
     const int32_t D = h->cfg.dim;
-    if (!is_bias_table(which)) return {h->tab[which], 0, D, h->ds};
-    if (!h->fat) return {h->tab[which], 0, 1, 1};
+    if (!is_bias_table(which)) {
+        if (h->emb16 && (which == GE_STATE_FOCUS || which == GE_STATE_CONTEXT)) return {h->tab[which], 0, D, h->es, true};
+        return {h->tab[which], 0, D, h->ds, false};
+    }
+    if (!h->fat) return {h->tab[which], 0, 1, 1, false};
     if (h->emb16) {
         const bool focus_side = which == GE_STATE_FBIAS || which == GE_STATE_GSQ_FBIAS;
         const bool the_bias = which == GE_STATE_FBIAS || which == GE_STATE_CBIAS;
-        return {h->tab[focus_side ? GE_STATE_GSQ_FOCUS : GE_STATE_GSQ_CONTEXT], the_bias ? D + 1 : D, 1, h->ds};
+        return {h->tab[focus_side ? GE_STATE_GSQ_FOCUS : GE_STATE_GSQ_CONTEXT], the_bias ? D + 1 : D, 1, h->ds, false};
     }
-    return {h->tab[FAT_HOME[which]], D, 1, h->ds};
+    return {h->tab[FAT_HOME[which]], D, 1, h->ds, false};
 }
 
-static ge_status ge_glove_create_impl(const ge_glove_cfg *cfg, const int32_t *I, const int32_t *J, const float *X,
-                          ge_glove **out) {
-    if (!out) return ge::fail(GE_ERR_ARG, "out is null");
-    *out = nullptr;
+// Table `which` between its device layout and a dense fp32 device buffer of tab_count[which] floats, as the API shows it (rows
+// [n x D] or a bias vector [n]), enqueued on the handle's stream.  fp32: gathered out of / scattered into the strided rows; bf16:
+// widened / rounded to nearest even, the hub rows of CONTEXT from / to their fp32 masters.
+enum CopyDir { TO_DENSE, FROM_DENSE };
+ge_status copy_table(ge_glove *h, int which, float *dense, CopyDir dir) {
+    const TableView v = view_of(h, which);
+    const int64_t n = h->tab_count[which];
+    const int32_t V = h->cfg.vocab_size, D = h->cfg.dim;
+    if (v.bf16) {
+        const dim3 grid((unsigned)std::min<int64_t>((n + 255) / 256, 8192));
+        uint16_t *rows16 = reinterpret_cast<uint16_t *>(v.base);
+        const bool hubs = which == GE_STATE_CONTEXT && h->n_hub > 0;
+        if (dir == TO_DENSE) {
+            hipLaunchKernelGGL(k_bf16_to_f32, grid, dim3(256), 0, h->stream, (const uint16_t *)rows16, dense, n, D, v.stride);
+            if (hubs) hipLaunchKernelGGL(k_hub_rows, dim3((unsigned)V), dim3(64), 0, h->stream, dense, h->hub32, h->dhub_index, V, D, 1);
+        } else {
+            if (hubs) hipLaunchKernelGGL(k_hub_rows, dim3((unsigned)V), dim3(64), 0, h->stream, dense, h->hub32, h->dhub_index, V, D, 0);
+            hipLaunchKernelGGL(k_f32_to_bf16, grid, dim3(256), 0, h->stream, (const float *)dense, rows16, n, D, v.stride);
+        }
+    } else {
+        const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 16384)));
+        hipLaunchKernelGGL(dir == TO_DENSE ? k_fat_copy<true> : k_fat_copy<false>, grid, dim3(256), 0, h->stream,
+                           v.base, n / v.ncols, (int32_t)v.stride, v.col0, v.ncols, dense);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_failed(dir == FROM_DENSE ? "state copy" : v.bf16 ? "bf16 -> fp32 conversion" : "row gather", e);
+    return GE_OK;
+}
+
+// get_state / set_state: table `which` to or from the caller's dense host array; returns with the stream drained
+ge_status state_io(ge_glove *h, int32_t which, float *host, int64_t count, CopyDir dir) {
+    GE_CHECK(check_handle(h));
+    if (which < 0 || which >= GE_STATE_COUNT || !host) return ge::fail(GE_ERR_ARG, "invalid state id %d or null buffer", which);
+    if (count != h->tab_count[which]) return ge::fail(GE_ERR_ARG, "state %d holds %lld floats, caller passed %lld", which, (long long)h->tab_count[which], (long long)count);
+    if (count == 0) return GE_OK;
+    const TableView v = view_of(h, which);
+    const size_t bytes = sizeof(float) * (size_t)count;
+    DeviceBuf stage;                                                  // a dense copy on the device, unless the table is one already
+    if (!v.dense()) GE_HIP(hipMalloc(&stage.p, bytes));
+    float *dev = v.dense() ? v.base : stage.f32();
+    hipError_t e = hipSuccess;
+    if (dir == FROM_DENSE) e = hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess && !v.dense()) GE_CHECK(copy_table(h, which, dev, dir));
+    if (e == hipSuccess && dir == TO_DENSE) e = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return hip_failed("state copy", e);
+    return GE_OK;
+}
+
+// (focus + context) / 2 of every row in a fresh device buffer (the caller frees it), enqueued on the handle's stream.
+ge_status extract_to_device(ge_glove *h, bool f64, void **out) {
+    GE_CHECK(check_handle(h));
+    if (h->rows != h->cfg.vocab_size)
+        return ge::fail(GE_ERR_STATE, "extract needs all focus rows on this handle (owned [%d,%d) of %d); gather shards first",
+                        h->cfg.row_begin, h->cfg.row_end, h->cfg.vocab_size);
+    const int64_t n = (int64_t)h->cfg.vocab_size * h->cfg.dim;
+    DeviceBuf d, stage[2];
+    GE_HIP(hipMalloc(&d.p, (size_t)n * (f64 ? sizeof(double) : sizeof(float))));
+    const int side[2] = {GE_STATE_FOCUS, GE_STATE_CONTEXT};
+    const float *src[2] = {h->tab[GE_STATE_FOCUS], h->tab[GE_STATE_CONTEXT]};
+    const bool temp = !view_of(h, GE_STATE_FOCUS).dense();          // both sides share one layout
+    if (temp)
+        for (int s = 0; s < 2; ++s) {
+            GE_HIP(hipMalloc(&stage[s].p, sizeof(float) * (size_t)n));
+            GE_CHECK(copy_table(h, side[s], stage[s].f32(), TO_DENSE));
+            src[s] = stage[s].f32();
+        }
+    const int blocks = (int)std::min<int64_t>((n + 255) / 256, 8192);
+    if (f64) hipLaunchKernelGGL(k_extract<double>, dim3(blocks), dim3(256), 0, h->stream, src[0], src[1], (double *)d.p, n);
+    else     hipLaunchKernelGGL(k_extract<float>,  dim3(blocks), dim3(256), 0, h->stream, src[0], src[1], d.f32(), n);
+    hipError_t e = hipGetLastError();
+    if (temp && e == hipSuccess) e = hipStreamSynchronize(h->stream);      // the temporaries may go once the kernel that reads them has run
+    if (e != hipSuccess) return hip_failed("extract", e);
+    *out = d.release();
+    return GE_OK;
+}
+
+ge_status extract_impl(ge_glove *h, void *out, bool f64) {
+    if (h && !out) return ge::fail(GE_ERR_ARG, "out is null");
+    DeviceBuf d;
+    GE_CHECK(extract_to_device(h, f64, &d.p));
+    const size_t bytes = (size_t)h->cfg.vocab_size * (size_t)h->cfg.dim * (f64 ? sizeof(double) : sizeof(float));
+    hipError_t e = hipMemcpyAsync(out, d.p, bytes, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return hip_failed("extract copy", e);
+    return GE_OK;
+}
+
+// ---- ge_glove_create, step by step (each step takes the handle; a failed step leaves whatever it allocated to ge_glove_destroy) ----
+
+// GE_GLOVE_TIMING=1: where ge_glove_create's time goes, to stderr (host clock; the stream is drained at each lap)
+struct CreateClock {
+    bool on;
+    hipStream_t stream;
+    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+    void lap(const char *what) {
+        if (!on) return;
+        (void)hipStreamSynchronize(stream);
+        const auto n = std::chrono::steady_clock::now();
+        std::fprintf(stderr, "[ge_glove_create] %-34s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(n - t).count());
+        t = n;
+    }
+};
+
+// The configuration and the nonzeros as the caller passed them; [*rb, *re) = the focus rows this handle owns.
+ge_status validate_config(const ge_glove_cfg *cfg, const int32_t *I, const int32_t *J, const float *X, int32_t *rb_out, int32_t *re_out) {
     if (!cfg) return ge::fail(GE_ERR_ARG, "cfg is null");
     if (cfg->vocab_size <= 0) return ge::fail(GE_ERR_ARG, "vocab_size must be > 0 (got %d)", cfg->vocab_size);
     if (cfg->dim <= 0) return ge::fail(GE_ERR_ARG, "No dimension specified (dim=%d)", cfg->dim);   // Configuration.check
@@ -1162,294 +1267,316 @@ static ge_status ge_glove_create_impl(const ge_glove_cfg *cfg, const int32_t *I,
             if (I[k] < rb || I[k] >= re) return ge::fail(GE_ERR_ARG, "I[%lld]=%d outside owned rows [%d,%d)", (long long)k, I[k], rb, re);
             if (J[k] < 0 || J[k] >= cfg->vocab_size) return ge::fail(GE_ERR_ARG, "J[%lld]=%d outside [0,%d)", (long long)k, J[k], cfg->vocab_size);
         }
-    ge_status st = ge::select_device(cfg->device);
-    if (st != GE_OK) return st;
+    *rb_out = rb; *re_out = re;
+    return GE_OK;
+}
 
-    ge_glove *h = new (std::nothrow) ge_glove();
-    if (!h) return ge::fail(GE_ERR_OOM, "host allocation failed");
-    h->cfg = *cfg;
-    h->emb16 = emb16;
-    h->fat = cfg->mode == GE_MODE_HOGWILD && fat_rows_fit(cfg->dim);
-    h->cfg.row_begin = rb; h->cfg.row_end = re;
-    h->rows = re - rb;
-    h->stream = (hipStream_t)cfg->stream;
-    const int32_t V = cfg->vocab_size, D = cfg->dim;
-    const int64_t N = cfg->nnz;
-    const bool moments = cfg->opt != GE_OPT_ADAGRAD;      // Adam / AMSGrad keep M2* next to M1*
-    const bool interleave = cfg->mode == GE_MODE_HOGWILD && (cfg->layout_flags & GE_LAYOUT_SEPARATE_TABLES) == 0;
-    const bool packed = (cfg->layout_flags & GE_LAYOUT_PACKED_RECORDS) != 0;
+// The kernel of a Hogwild handle and the geometry of every handle's rows and records (fat, rw, ds, e16, es): a function of cfg alone.
+ge_status plan_geometry(ge_glove *h) {
+    const ge_glove_cfg &cfg = h->cfg;
+    const int32_t D = cfg.dim;
+    h->emb16 = cfg.emb_dtype == GE_DTYPE_BF16;
+    if (h->hogwild()) {
+        h->hw = pick_hogwild(D, cfg.opt, h->emb16);
+        if (!h->hw.fn) return ge::fail(GE_ERR_ARG, "dim %d not supported by the Hogwild kernel (max 1024 for dim%%4==0, 512 for other even dims, 256 for odd dims)", D);
+        h->fat = h->hw.fat;
+    } else if ((size_t)D * sizeof(float) > 64 * 1024) {
+        return ge::fail(GE_ERR_ARG, "dim %d too large for deterministic mode", D);
+    }
+    const bool interleave = h->interleaved();
+    const bool packed = (cfg.layout_flags & GE_LAYOUT_PACKED_RECORDS) != 0;
     h->rw = h->fat ? D + 4 : D;
     // An fp32 fat row as wide as the whole 64-byte lines that hold it (D = 200: 208 floats): every row store then writes whole
     // lines and a row shares no line with its accumulator row.  More bytes, less time: D = 100 (112 instead of 104 floats) 29.8 /
     // 30.4 -> 27.5 / 27.5 ms, D = 200 48.9 / 53.8 -> 47.8 / 47.8 ms (tools/r02/rw_probe.sh).  Not for bf16 rows (no
     // gain measured) and not where the padding would exceed 10 %.
-    if (h->fat && !emb16 && !packed && D % 4 == 0) {
+    if (h->fat && !h->emb16 && !packed && D % 4 == 0) {
         const int32_t lines = (D + 1 + 15) / 16 * 16;
         if ((int64_t)lines * 10 <= (int64_t)(D + 4) * 11) h->rw = lines;
     }
-    h->ds = h->rw * (interleave ? (moments ? 3 : 2) : 1);
+    h->ds = h->rw * (interleave ? (h->moments() ? 3 : 2) : 1);
     // bf16 rows in records: [bf16 row, padded to 16 bytes | fp32 accumulator row]; e16 = bf16 elements of the padded row
-    const int32_t e16 = (D + 7) / 8 * 8;
-    if (emb16) h->ds = interleave ? e16 / 2 + h->rw : h->rw;                                             // rw: the accumulator row (fat: + its two scalars)
+    h->e16 = (D + 7) / 8 * 8;
+    if (h->emb16) h->ds = interleave ? h->e16 / 2 + h->rw : h->rw;                                      // rw: the accumulator row (fat: + its two scalars)
     // A record starts on a 64-byte boundary: a wave's 16-byte-per-lane row access then covers whole 64-byte requests.  Records of
     // 1 632 bytes (D = 200) start on odd 32-byte sectors half of the time; rounding them up to 1 664 took the epoch from 60.9 to
     // 49.2 ms on one box and from 60.8 to 54.6 on another (tools/r02/align_probe.sh, kernel_ab.sh).  Rounding further
     // (128 bytes and more) gains nothing at D = 200 and loses 5 % on the 1 216-byte records of bf16 rows.  The padding is never touched.
     if (interleave && !packed) h->ds = (h->ds + 15) / 16 * 16;
-    if (const char *pad = std::getenv("GE_RECORD_PAD_LINES")) if (interleave && !packed) h->ds += 16 * std::max(0, std::atoi(pad));   // experiment: record stride + n x 64 B
-    if (emb16) h->es = interleave ? 2 * h->ds : D;
-
-    // GE_GLOVE_TIMING=1: where ge_glove_create's time goes, to stderr (host clock; the stream is drained at each lap)
-    struct CreateClock {
-        bool on = std::getenv("GE_GLOVE_TIMING") != nullptr;
-        hipStream_t stream = nullptr;
-        std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-        void lap(const char *what) {
-            if (!on) return;
-            (void)hipStreamSynchronize(stream);
-            const auto n = std::chrono::steady_clock::now();
-            std::fprintf(stderr, "[ge_glove_create] %-34s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(n - t).count());
-            t = n;
-        }
-    } clk;
-    clk.stream = h->stream;
-    // every failure below frees what the handle owns so far (ge_glove_destroy walks h->owned)
-#define GE_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { ge_status _s = ge::fail(_e == hipErrorOutOfMemory ? GE_ERR_OOM : GE_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); ge_glove_destroy(h); return _s; } } while (0)
-
-    hipDeviceProp_t prop;
-    GE_TRY(hipGetDeviceProperties(&prop, cfg->device));
-    h->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-
-    GE_TRY(hipEventCreate(&h->ev0));
-    GE_TRY(hipEventCreate(&h->ev1));
-
-    // ---- tables, allocated once, in their final layout ------------------------------------------------------------
-    // fp32 row tables: `rw` floats per row (fat rows carry the bias at [D]); unless GE_LAYOUT_SEPARATE_TABLES a side is ONE
-    // allocation of records [row | accumulator row (| second moment row)], stride ds = 2 or 3 rw.  bf16 rows: records
-    // [bf16 row padded to 16 bytes | fp32 accumulator row, fat: gradSq (D) | its bias accumulator | the bias | 2 x 0].
-    const int64_t counts[GE_STATE_COUNT] = {
-        (int64_t)h->rows * D, (int64_t)V * D, h->rows, V, (int64_t)h->rows * D, (int64_t)V * D, h->rows, V,
-        moments ? (int64_t)h->rows * D : 0, moments ? (int64_t)V * D : 0, moments ? h->rows : 0, moments ? V : 0};
-    for (int t = 0; t < GE_STATE_COUNT; ++t) h->tab_count[t] = counts[t];
-    {
-        static const int ROWT[2][3] = {{GE_STATE_FOCUS, GE_STATE_GSQ_FOCUS, GE_STATE_M2_FOCUS}, {GE_STATE_CONTEXT, GE_STATE_GSQ_CONTEXT, GE_STATE_M2_CONTEXT}};
-        static const int BIAST[2][3] = {{GE_STATE_FBIAS, GE_STATE_GSQ_FBIAS, GE_STATE_M2_FBIAS}, {GE_STATE_CBIAS, GE_STATE_GSQ_CBIAS, GE_STATE_M2_CBIAS}};
-        const int n_aux = moments ? 3 : 2;
-        for (int side = 0; side < 2; ++side) {
-            const size_t nr = side == 0 ? (size_t)h->rows : (size_t)V;
-            if (interleave) {
-                // Where the driver places a table decides which of two epoch times the handle gets (same process, same
-                // virtual address, 48 or 54 ms at the bench size).  So a large table is allocated up to six times, each candidate
-                // while the earlier ones are still held (else the driver hands the same pages back), a millisecond of what an epoch
-                // does to it is timed on each (0.91 - 0.97 ms on the good placements, 1.04 - 1.11 ms on the others), the fastest is kept.
-                float *blk = nullptr;
-                const size_t bytes = nr * (size_t)h->ds * sizeof(float);
-                const char *alloc_env = std::getenv("GE_TABLE_ALLOC");
-                const bool contiguous = alloc_env && std::strcmp(alloc_env, "contiguous") == 0;
-                // Bounds: the candidates of one table together stay under 24 GB (allocating and freeing an 8 GB table costs a quarter
-                // of a second) AND under half of what the device has free right now (another process may share the GPU; a candidate
-                // that cannot be allocated ends the search with what there is); a table too large for a second candidate gets one.
-                size_t free_b = 0, total_b = 0;
-                if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
-                const size_t budget = std::min<size_t>((size_t)24 << 30, free_b / 2);
-                const int tries = ((cfg->layout_flags & GE_LAYOUT_FIRST_PLACEMENT) || bytes < ((size_t)64 << 20)) ? 1
-                                : (int)std::max<size_t>(1, std::min<size_t>(6, budget / bytes));
-                float *cand[6] = {}; float cand_ms[6] = {};
-                int n_cand = 0, best = 0;
-                for (int t = 0; t < tries; ++t) {
-                    hipError_t me = hipErrorUnknown;
-                    if (contiguous) {                                       // experiment (GE_TABLE_ALLOC=contiguous): physically contiguous VRAM
-                        me = hipExtMallocWithFlags((void **)&cand[t], bytes, hipDeviceMallocContiguous);
-                        if (me != hipSuccess) { (void)hipGetLastError(); cand[t] = nullptr; }
-                    }
-                    if (me != hipSuccess) me = hipMalloc((void **)&cand[t], bytes);
-                    if (me != hipSuccess) { (void)hipGetLastError(); cand[t] = nullptr; break; }     // no room for another candidate: keep what there is
-                    ++n_cand;
-                    h->owned.push_back((void *)cand[t]);               // the handle owns every candidate until the losers are freed below
-                    if (tries > 1) {
-                        const int32_t rec_bytes = (int32_t)std::min<int64_t>((int64_t)h->ds * 4, 4096);
-                        float ms_min = 1e30f;
-                        for (int rep = 0; rep < 3; ++rep) {
-                            GE_TRY(hipEventRecord(h->ev0, h->stream));
-                            hipLaunchKernelGGL(k_probe_records, dim3((unsigned)h->num_cus * 5), dim3(256), 0, h->stream, cand[t], (int64_t)nr, (int64_t)h->ds, rec_bytes, 384, 0x5EEDu + rep);
-                            GE_TRY(hipEventRecord(h->ev1, h->stream));
-                            GE_TRY(hipEventSynchronize(h->ev1));
-                            float ms = 0.0f; GE_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-                            ms_min = std::min(ms_min, ms);
-                        }
-                        cand_ms[t] = ms_min;
-                        if (cand_ms[t] < cand_ms[best]) best = t;
-                        float slowest = cand_ms[0];
-                        for (int u = 1; u <= t; ++u) slowest = std::max(slowest, cand_ms[u]);
-                        if (cand_ms[best] < 0.88f * slowest) break;        // both kinds seen and a fast one in hand (they lie 15 - 20 % apart)
-                        if (t >= 2 && cand_ms[best] > 0.98f * slowest) break;  // three candidates within 2 %: a box that has one kind only
-                    }
-                }
-                if (n_cand == 0) { ge_status _s = ge::fail(GE_ERR_OOM, "hipMalloc of a %zu-byte record table failed", bytes); ge_glove_destroy(h); return _s; }
-                float worst = cand_ms[best];
-                for (int t = 0; t < n_cand; ++t) {
-                    worst = std::max(worst, cand_ms[t]);
-                    if (t == best) continue;
-                    h->owned.erase(std::find(h->owned.begin(), h->owned.end(), (void *)cand[t]));
-                    (void)hipFree(cand[t]);
-                }
-                blk = cand[best];
-                h->placements += n_cand; h->place_best_ms += cand_ms[best]; h->place_worst_ms += worst;
-                if (emb16) { h->tab[ROWT[side][0]] = blk; h->tab[ROWT[side][1]] = blk + e16 / 2; }     // the bf16 row leads its record
-                else for (int a = 0; a < n_aux; ++a) h->tab[ROWT[side][a]] = blk + (size_t)a * h->rw;
-            } else {
-                for (int a = 0; a < n_aux; ++a) {
-                    if (a == 0 && emb16) { uint16_t *t16 = nullptr; GE_TRY(h->alloc(&t16, nr * (size_t)D)); h->tab[ROWT[side][0]] = reinterpret_cast<float *>(t16); }
-                    else GE_TRY(h->alloc(&h->tab[ROWT[side][a]], nr * (size_t)h->ds));
-                }
-            }
-            if (!h->fat) for (int a = 0; a < n_aux; ++a) GE_TRY(h->alloc(&h->tab[BIAST[side][a]], nr));
-        }
-    }
-    clk.lap("tables (placement search)");
-    const size_t nn = (size_t)std::max<int64_t>(N, 1);
-    GE_TRY(h->alloc(&h->dcost, 2));
-    GE_TRY(h->alloc(&h->djob, (size_t)cfg->threads));
-
-    if (cfg->mode == GE_MODE_HOGWILD) {
-        h->hw_fn = pick_hogwild(D, cfg->opt, emb16, &h->hw_vw, &h->hw_nch);
-        if (!h->hw_fn) { ge_glove_destroy(h); return ge::fail(GE_ERR_ARG, "dim %d not supported by the Hogwild kernel (max 1024 for dim%%4==0, 512 for other even dims, 256 for odd dims)", D); }
-        // One wavefront = one sequential worker.  Never more workers than N/2048: a small matrix must
-        // not degenerate into one giant stale batch (the JVM has at most #cores updates in flight).
-        const int groups_per_block = 4;
-        const int64_t chunks = (N + RUN_CHUNK - 1) / RUN_CHUNK;
-        int occ = 0;
-        h->hw_blocks_per_cu = cfg->blocks_per_cu > 0 ? cfg->blocks_per_cu : 4;
-        if (cfg->blocks_per_cu == 0 && hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void *>(h->hw_fn), 256, 0) == hipSuccess && occ > 0)
-            h->hw_blocks_per_cu = occ;                   // every worker resident: one wave of blocks
-        int64_t blocks = std::min<int64_t>((chunks + 3) / 4, (int64_t)h->num_cus * h->hw_blocks_per_cu);
-        blocks = std::min<int64_t>(blocks, std::max<int64_t>(1, N / 2048 / groups_per_block));
-        h->hw_blocks = (int)std::max<int64_t>(blocks, 1);
-        h->hw_workers = h->hw_blocks * 4;
-        if (cfg->workers > 0) {                       // explicit worker count (tests, reproducibility)
-            h->hw_workers = (int)std::min<int64_t>(cfg->workers, (int64_t)h->num_cus * 32);
-            h->hw_blocks = (h->hw_workers + 3) / 4;
-        } else if (cfg->workers < 0) {                // fill the device but leave -workers wavefront slots to kernels
-            h->hw_blocks = (int)std::max<int64_t>(1, (int64_t)h->hw_blocks - (-(int64_t)cfg->workers + 3) / 4);   // running beside (collectives)
-            h->hw_workers = h->hw_blocks * 4;
-        }
-        // (0.05 -- five times the hub columns -- takes a fifth off the Hogwild lag, C2 epoch 32: 1.068 -> 1.055 of the sequential oracle's
-        // cost, and is free on the faster kind of placement (48.0 -> 48.3 ms) but costs 4 - 7 % on the slower kind (54.9 -> 57 - 58.7 ms,
-        // tools/r03/theta_modes.py): the default stays 0.25)
-        const double theta = cfg->hot_theta > 0 ? (double)cfg->hot_theta : 0.25;
-        const double stale_budget = cfg->stale_budget > 0 ? (double)cfg->stale_budget : 2000.0;
-        h->blocked = cfg->shuffle == GE_SHUFFLE_DEVICE;
-        if (h->blocked) {
-            ge::LayoutRequest rq{};
-            rq.V = V; rq.row_begin = rb; rq.row_end = re; rq.N = N; rq.cost = cfg->cost; rq.xmax = cfg->xmax;
-            rq.hot_columns = cfg->hot_columns; rq.hot_theta = theta; rq.stale_budget = stale_budget; rq.flush_every = cfg->flush_every;
-            rq.workers = h->hw_workers;
-            rq.shared_rows = (cfg->layout_flags & GE_LAYOUT_PLAIN_LONG_ROWS) ? 0 : 1;
-            rq.pack_rows = (cfg->layout_flags & GE_LAYOUT_FIXED_CUTS) ? 0 : 1;
-            rq.want_hub_index = emb16;
-            st = ge::build_blocked_layout(rq, I, J, X, h->stream, &h->lay);
-            if (st != GE_OK) { ge_glove_destroy(h); return st; }
-            h->n_chunks = h->lay.n_chunks; h->n_hchunks = h->lay.n_hchunks;
-            h->hot_cols = h->lay.hot_cols; h->hot_nnz = h->lay.hot_nnz; h->hot_threshold = h->lay.hot_threshold;
-            h->flush_every = h->lay.flush_min;
-            if (emb16) { h->host_hub_index.swap(h->lay.hub_index); h->n_hub = h->lay.n_hub; }
-        } else {
-            // general order (Java permutation / matrix order): the resident side is always the context row, hub columns are keyed ~j
-            std::vector<int32_t> cnt((size_t)V, 0);
-            std::vector<uint8_t> hotcol((size_t)V, 0);
-            if (N > 0 && cfg->hot_columns != GE_HOT_NONE) {
-                const int64_t thr = cfg->hot_columns == GE_HOT_ALL ? 0
-                                  : std::max<int64_t>(2, (int64_t)std::ceil(theta * (double)N / (double)h->hw_workers));
-                for (int64_t k = 0; k < N; ++k) ++cnt[(size_t)J[k]];
-                for (int32_t v = 0; v < V; ++v)
-                    if (cnt[(size_t)v] >= thr && cnt[(size_t)v] > 0) { hotcol[(size_t)v] = 1; ++h->hot_cols; h->hot_nnz += cnt[(size_t)v]; }
-                h->hot_threshold = thr;
-            }
-            h->flush_every = cfg->flush_every > 0 ? std::min<int32_t>(cfg->flush_every, RUN_CHUNK) : RUN_CHUNK;
-            if (cfg->flush_every == 0)
-                for (int32_t v = 0; v < V; ++v) if (hotcol[(size_t)v]) {
-                    const double K = std::max(1.0, (double)cnt[(size_t)v] * (double)h->hw_workers / (double)std::max<int64_t>(N, 1));
-                    h->flush_every = std::min<int>(h->flush_every, (int)std::min<double>(RUN_CHUNK, std::max<double>(4.0, std::floor(stale_budget / K))));
-                }
-            h->host_key.assign(J, J + N);
-            for (int64_t k = 0; k < N; ++k) if (hotcol[(size_t)J[k]]) h->host_key[(size_t)k] = ~J[k];
-            h->n_chunks = chunks; h->n_hchunks = 0;
-        }
-    } else if ((size_t)D * sizeof(float) > 64 * 1024) {
-        ge_glove_destroy(h);
-        return ge::fail(GE_ERR_ARG, "dim %d too large for deterministic mode", D);
-    }
-    clk.lap("epoch layout");
-    if (!h->blocked) {
-        GE_TRY(h->alloc(&h->dI, nn)); GE_TRY(h->alloc(&h->dJ, nn)); GE_TRY(h->alloc(&h->dX, nn));
-        if (N > 0) {
-            GE_TRY(hipMemcpyAsync(h->dI, I, sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice, h->stream));
-            GE_TRY(hipMemcpyAsync(h->dJ, h->host_key.empty() ? J : h->host_key.data(), sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice, h->stream));
-            GE_TRY(hipMemcpyAsync(h->dX, X, sizeof(float) * (size_t)N, hipMemcpyHostToDevice, h->stream));
-            if (cfg->mode == GE_MODE_HOGWILD) {
-                GE_TRY(h->alloc(&h->dL, nn)); GE_TRY(h->alloc(&h->dW, nn));
-                const int blocks = (int)std::min<int64_t>((N + 255) / 256, 8192);
-                hipLaunchKernelGGL(k_cost_terms, dim3(blocks), dim3(256), 0, h->stream, h->dX, N, cfg->cost, cfg->xmax, h->dL, h->dW);
-            }
-            GE_TRY(hipStreamSynchronize(h->stream));
-        }
-    }
-    if (cfg->shuffle == GE_SHUFFLE_JAVA) {
-        GE_TRY(h->alloc(&h->dperm, nn));
-        h->perm.resize((size_t)N);
-        for (int64_t k = 0; k < N; ++k) h->perm[(size_t)k] = (int32_t)k;     // Permutation ctor
-    }
-
-    // --- parameter init in the reference's draw order, straight into the final layout; the context side covers all V
-    //     rows, the focus side only the owned rows (same values a single-GPU run would hold there).
-    const uint64_t s0 = ge::JavaRandom::scramble(cfg->seed);
-    if (emb16) {
-        GE_TRY(h->alloc(&h->dhub_index, (size_t)V));
-        GE_TRY(hipMemcpyAsync(h->dhub_index, h->host_hub_index.data(), sizeof(int32_t) * (size_t)V, hipMemcpyHostToDevice, h->stream));
-        GE_TRY(h->alloc(&h->hub32, (size_t)std::max<int64_t>((int64_t)h->n_hub * D, 1)));
-    }
-    {
-        // Adagrad ctor: gradSq = 1 (Adagrad.java:27-33); Adam / AMSGrad ctors: every moment = 0 (new float[]).  Before the parameter
-        // init: a bf16 handle's bias lives in the accumulator row and must survive the fill.
-        const float v0 = moments ? 0.0f : 1.0f;
-        for (int t : {GE_STATE_GSQ_FOCUS, GE_STATE_GSQ_CONTEXT, GE_STATE_M2_FOCUS, GE_STATE_M2_CONTEXT}) {
-            if (!h->tab[t]) continue;
-            const int64_t nr = h->tab_count[t] / D;
-            const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((nr * h->rw + 255) / 256, 8192));
-            hipLaunchKernelGGL(k_fill_rows, dim3(blocks), dim3(256), 0, h->stream, h->tab[t], nr, (int64_t)h->ds, h->fat ? D + 1 : D, h->rw, v0);
-        }
-        for (int t : {GE_STATE_GSQ_FBIAS, GE_STATE_GSQ_CBIAS, GE_STATE_M2_FBIAS, GE_STATE_M2_CBIAS}) {
-            if (!h->tab[t]) continue;
-            const int64_t n = h->tab_count[t];
-            hipLaunchKernelGGL(k_fill, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 4096))), dim3(256), 0, h->stream, h->tab[t], n, v0);
-        }
-        const int64_t stride = emb16 ? h->es : h->ds;
-        const int32_t bias_col = (h->fat && !emb16) ? D : -1;        // fp32 fat rows: the bias is a column of the row being written
-        const Home fb = home_of(h, GE_STATE_FBIAS), cb = home_of(h, GE_STATE_CBIAS);
-        void *foc = h->tab[GE_STATE_FOCUS], *ctx = h->tab[GE_STATE_CONTEXT];
-        auto launch = [&](void *f, void *c, int32_t row0, int32_t nrows) {
-            const dim3 g((unsigned)((nrows + 127) / 128)), b(128);
-            if (emb16) hipLaunchKernelGGL(k_init_java<true>, g, b, 0, h->stream, f, c, fb.base + fb.col0, cb.base + cb.col0, (int64_t)fb.stride, rb,
-                                          row0, nrows, D, stride, bias_col, h->rw, s0, (const int32_t *)h->dhub_index, h->hub32);
-            else hipLaunchKernelGGL(k_init_java<false>, g, b, 0, h->stream, f, c, fb.base ? fb.base + fb.col0 : nullptr, cb.base ? cb.base + cb.col0 : nullptr, (int64_t)fb.stride, rb,
-                                    row0, nrows, D, stride, bias_col, h->rw, s0, (const int32_t *)nullptr, (float *)nullptr);
-        };
-        if (h->rows == V) launch(foc, ctx, 0, V);
-        else { launch(nullptr, ctx, 0, V); launch(foc, nullptr, rb, h->rows); }
-    }
-    GE_TRY(hipGetLastError());
-    GE_TRY(hipStreamSynchronize(h->stream));
-    h->rng.s = ge::JavaRandom::jump(s0, (uint64_t)V * (uint64_t)(2 + 2 * D));
-
-    clk.lap("init and the rest");
-#undef GE_TRY
-    *out = h;
+    if (h->emb16) h->es = interleave ? 2 * h->ds : D;
     return GE_OK;
 }
 
-static ge_status ge_glove_epoch_impl(ge_glove *h, int32_t iteration, double *cost_sum) {
-    ge_status st = check_handle(h);
-    if (st != GE_OK) return st;
+// Where the driver places a table decides which of two epoch times the handle gets (same process, same virtual
+// address, 48 or 54 ms at the bench size).  So a large table is allocated up to six times, each candidate while the earlier ones
+// are still held (else the driver hands the same pages back), a millisecond of what an epoch does to it is timed on each (0.91 -
+// 0.97 ms on the good placements, 1.04 - 1.11 ms on the others), the fastest is kept.
+struct Placement { float *block = nullptr; int tried = 0; float best_ms = 0.0f, worst_ms = 0.0f; };
+ge_status place_record_table(ge_glove *h, size_t rows, Placement *out) {
+    const size_t bytes = rows * (size_t)h->ds * sizeof(float);
+    // Bounds: the candidates of one table together stay under 24 GB (allocating and freeing an 8 GB table costs a quarter
+    // of a second) AND under half of what the device has free right now (another process may share the GPU; a candidate
+    // that cannot be allocated ends the search with what there is); a table too large for a second candidate gets one.
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
+    const size_t budget = std::min<size_t>((size_t)24 << 30, free_b / 2);
+    const int tries = ((h->cfg.layout_flags & GE_LAYOUT_FIRST_PLACEMENT) || bytes < ((size_t)64 << 20)) ? 1
+                    : (int)std::max<size_t>(1, std::min<size_t>(6, budget / bytes));
+    float *cand[6] = {}; float cand_ms[6] = {};
+    int n_cand = 0, best = 0;
+    for (int t = 0; t < tries; ++t) {
+        if (hipMalloc((void **)&cand[t], bytes) != hipSuccess) { (void)hipGetLastError(); cand[t] = nullptr; break; }     // no room for another candidate: keep what there is
+        ++n_cand;
+        h->owned.push_back((void *)cand[t]);               // the handle owns every candidate until the losers are freed below
+        if (tries == 1) break;
+        const int32_t rec_bytes = (int32_t)std::min<int64_t>((int64_t)h->ds * 4, 4096);
+        float ms_min = 1e30f;
+        for (int rep = 0; rep < 3; ++rep) {
+            GE_HIP(hipEventRecord(h->ev0, h->stream));
+            hipLaunchKernelGGL(k_probe_records, dim3((unsigned)h->num_cus * 5), dim3(256), 0, h->stream, cand[t], (int64_t)rows, (int64_t)h->ds, rec_bytes, 384, 0x5EEDu + rep);
+            GE_HIP(hipEventRecord(h->ev1, h->stream));
+            GE_HIP(hipEventSynchronize(h->ev1));
+            float ms = 0.0f; GE_HIP(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+            ms_min = std::min(ms_min, ms);
+        }
+        cand_ms[t] = ms_min;
+        if (cand_ms[t] < cand_ms[best]) best = t;
+        const float slowest = *std::max_element(cand_ms, cand_ms + t + 1);
+        if (cand_ms[best] < 0.88f * slowest) break;        // both kinds seen and a fast one in hand (they lie 15 - 20 % apart)
+        if (t >= 2 && cand_ms[best] > 0.98f * slowest) break;  // three candidates within 2 %: a box that has one kind only
+    }
+    if (n_cand == 0) return ge::fail(GE_ERR_OOM, "hipMalloc of a %zu-byte record table failed", bytes);
+    for (int t = 0; t < n_cand; ++t) {
+        if (t == best) continue;
+        h->owned.erase(std::find(h->owned.begin(), h->owned.end(), (void *)cand[t]));
+        (void)hipFree(cand[t]);
+    }
+    *out = {cand[best], n_cand, cand_ms[best], *std::max_element(cand_ms, cand_ms + n_cand)};
+    return GE_OK;
+}
+
+// Tables, allocated once, in their final layout.  fp32 row tables: `rw` floats per row (fat rows carry the bias at [D]); unless
+// GE_LAYOUT_SEPARATE_TABLES a side is ONE allocation of records [row | accumulator row (| second moment row)], stride ds = 2 or
+// 3 rw.  bf16 rows: records [bf16 row padded to 16 bytes | fp32 accumulator row, fat: gradSq (D) | its bias accumulator | the
+// bias | 2 x 0].
+ge_status alloc_tables(ge_glove *h) {
+    const int32_t V = h->cfg.vocab_size, D = h->cfg.dim;
+    static const int ROWT[2][3] = {{GE_STATE_FOCUS, GE_STATE_GSQ_FOCUS, GE_STATE_M2_FOCUS}, {GE_STATE_CONTEXT, GE_STATE_GSQ_CONTEXT, GE_STATE_M2_CONTEXT}};
+    static const int BIAST[2][3] = {{GE_STATE_FBIAS, GE_STATE_GSQ_FBIAS, GE_STATE_M2_FBIAS}, {GE_STATE_CBIAS, GE_STATE_GSQ_CBIAS, GE_STATE_M2_CBIAS}};
+    const int n_aux = h->moments() ? 3 : 2;
+    for (int side = 0; side < 2; ++side) {
+        const size_t nr = side == 0 ? (size_t)h->rows : (size_t)V;
+        for (int a = 0; a < n_aux; ++a) { h->tab_count[ROWT[side][a]] = (int64_t)nr * D; h->tab_count[BIAST[side][a]] = (int64_t)nr; }   // what the API shows
+        if (h->interleaved()) {
+            Placement pl;
+            GE_CHECK(place_record_table(h, nr, &pl));
+            h->placements += pl.tried; h->place_best_ms += pl.best_ms; h->place_worst_ms += pl.worst_ms;
+            if (h->emb16) { h->tab[ROWT[side][0]] = pl.block; h->tab[ROWT[side][1]] = pl.block + h->e16 / 2; }     // the bf16 row leads its record
+            else for (int a = 0; a < n_aux; ++a) h->tab[ROWT[side][a]] = pl.block + (size_t)a * h->rw;
+        } else {
+            for (int a = 0; a < n_aux; ++a) {
+                if (a == 0 && h->emb16) { uint16_t *t16 = nullptr; GE_HIP(h->alloc(&t16, nr * (size_t)D)); h->tab[ROWT[side][0]] = reinterpret_cast<float *>(t16); }
+                else GE_HIP(h->alloc(&h->tab[ROWT[side][a]], nr * (size_t)h->ds));
+            }
+        }
+        if (!h->fat) for (int a = 0; a < n_aux; ++a) GE_HIP(h->alloc(&h->tab[BIAST[side][a]], nr));
+    }
+    return GE_OK;
+}
+
+// One wavefront = one sequential worker.  Never more workers than N/2048: a small matrix must
+// not degenerate into one giant stale batch (the JVM has at most #cores updates in flight).
+void plan_workers(ge_glove *h) {
+    const ge_glove_cfg &cfg = h->cfg;
+    const int64_t N = cfg.nnz;
+    const int groups_per_block = 4;
+    const int64_t chunks = (N + RUN_CHUNK - 1) / RUN_CHUNK;
+    int occ = 0;
+    h->hw_blocks_per_cu = cfg.blocks_per_cu > 0 ? cfg.blocks_per_cu : 4;
+    if (cfg.blocks_per_cu == 0 && hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void *>(h->hw.fn), 256, 0) == hipSuccess && occ > 0)
+        h->hw_blocks_per_cu = occ;                   // every worker resident: one wave of blocks
+    int64_t blocks = std::min<int64_t>((chunks + 3) / 4, (int64_t)h->num_cus * h->hw_blocks_per_cu);
+    blocks = std::min<int64_t>(blocks, std::max<int64_t>(1, N / 2048 / groups_per_block));
+    h->hw_blocks = (int)std::max<int64_t>(blocks, 1);
+    h->hw_workers = h->hw_blocks * 4;
+    if (cfg.workers > 0) {                        // explicit worker count (tests, reproducibility)
+        h->hw_workers = (int)std::min<int64_t>(cfg.workers, (int64_t)h->num_cus * 32);
+        h->hw_blocks = (h->hw_workers + 3) / 4;
+    } else if (cfg.workers < 0) {                 // fill the device but leave -workers wavefront slots to kernels
+        h->hw_blocks = (int)std::max<int64_t>(1, (int64_t)h->hw_blocks - (-(int64_t)cfg.workers + 3) / 4);   // running beside (collectives)
+        h->hw_workers = h->hw_blocks * 4;
+    }
+}
+
+// The order a Hogwild epoch visits the nonzeros in.  Device shuffle: the blocked layout of ge_layout.h, built on the device.
+// General order (Java permutation / matrix order): the resident side is always the context row, hub columns are keyed ~j.
+ge_status plan_epoch_layout(ge_glove *h, const int32_t *I, const int32_t *J, const float *X) {
+    const ge_glove_cfg &cfg = h->cfg;
+    const int32_t V = cfg.vocab_size;
+    const int64_t N = cfg.nnz;
+    // (0.05 -- five times the hub columns -- takes a fifth off the Hogwild lag, C2 epoch 32: 1.068 -> 1.055 of the sequential oracle's
+    // cost, and is free on the faster kind of placement (48.0 -> 48.3 ms) but costs 4 - 7 % on the slower kind (54.9 -> 57 - 58.7 ms,
+    // tools/r03/theta_modes.py): the default stays 0.25)
+    const double theta = cfg.hot_theta > 0 ? (double)cfg.hot_theta : 0.25;
+    const double stale_budget = cfg.stale_budget > 0 ? (double)cfg.stale_budget : 2000.0;
+    h->blocked = cfg.shuffle == GE_SHUFFLE_DEVICE;
+    if (h->blocked) {
+        ge::LayoutRequest rq{};
+        rq.V = V; rq.row_begin = cfg.row_begin; rq.row_end = cfg.row_end; rq.N = N; rq.cost = cfg.cost; rq.xmax = cfg.xmax;
+        rq.hot_columns = cfg.hot_columns; rq.hot_theta = theta; rq.stale_budget = stale_budget; rq.flush_every = cfg.flush_every;
+        rq.workers = h->hw_workers;
+        rq.shared_rows = (cfg.layout_flags & GE_LAYOUT_PLAIN_LONG_ROWS) ? 0 : 1;
+        rq.pack_rows = (cfg.layout_flags & GE_LAYOUT_FIXED_CUTS) ? 0 : 1;
+        rq.want_hub_index = h->emb16;
+        GE_CHECK(ge::build_blocked_layout(rq, I, J, X, h->stream, &h->lay));
+        h->n_chunks = h->lay.n_chunks; h->n_hchunks = h->lay.n_hchunks;
+        h->hot_cols = h->lay.hot_cols; h->hot_nnz = h->lay.hot_nnz; h->hot_threshold = h->lay.hot_threshold;
+        h->flush_every = h->lay.flush_min;
+        if (h->emb16) { h->host_hub_index.swap(h->lay.hub_index); h->n_hub = h->lay.n_hub; }
+        return GE_OK;
+    }
+    std::vector<int32_t> cnt((size_t)V, 0);
+    std::vector<uint8_t> hotcol((size_t)V, 0);
+    if (N > 0 && cfg.hot_columns != GE_HOT_NONE) {
+        const int64_t thr = cfg.hot_columns == GE_HOT_ALL ? 0
+                          : std::max<int64_t>(2, (int64_t)std::ceil(theta * (double)N / (double)h->hw_workers));
+        for (int64_t k = 0; k < N; ++k) ++cnt[(size_t)J[k]];
+        for (int32_t v = 0; v < V; ++v)
+            if (cnt[(size_t)v] >= thr && cnt[(size_t)v] > 0) { hotcol[(size_t)v] = 1; ++h->hot_cols; h->hot_nnz += cnt[(size_t)v]; }
+        h->hot_threshold = thr;
+    }
+    h->flush_every = cfg.flush_every > 0 ? std::min<int32_t>(cfg.flush_every, RUN_CHUNK) : RUN_CHUNK;
+    if (cfg.flush_every == 0)
+        for (int32_t v = 0; v < V; ++v) if (hotcol[(size_t)v]) {
+            const double K = std::max(1.0, (double)cnt[(size_t)v] * (double)h->hw_workers / (double)std::max<int64_t>(N, 1));
+            h->flush_every = std::min<int>(h->flush_every, (int)std::min<double>(RUN_CHUNK, std::max<double>(4.0, std::floor(stale_budget / K))));
+        }
+    h->host_key.assign(J, J + N);
+    for (int64_t k = 0; k < N; ++k) if (hotcol[(size_t)J[k]]) h->host_key[(size_t)k] = ~J[k];
+    h->n_chunks = (N + RUN_CHUNK - 1) / RUN_CHUNK; h->n_hchunks = 0;
+    return GE_OK;
+}
+
+// General order: the nonzeros as the caller passed them (J replaced by the hub keys), and the Hogwild kernel's cost terms.
+// (The blocked layout holds its own re-ordered copies.)
+ge_status upload_nonzeros(ge_glove *h, const int32_t *I, const int32_t *J, const float *X) {
+    const int64_t N = h->cfg.nnz;
+    const size_t nn = (size_t)std::max<int64_t>(N, 1);
+    GE_HIP(h->alloc(&h->dI, nn)); GE_HIP(h->alloc(&h->dJ, nn)); GE_HIP(h->alloc(&h->dX, nn));
+    if (N == 0) return GE_OK;
+    GE_HIP(hipMemcpyAsync(h->dI, I, sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice, h->stream));
+    GE_HIP(hipMemcpyAsync(h->dJ, h->host_key.empty() ? J : h->host_key.data(), sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice, h->stream));
+    GE_HIP(hipMemcpyAsync(h->dX, X, sizeof(float) * (size_t)N, hipMemcpyHostToDevice, h->stream));
+    if (h->hogwild()) {
+        GE_HIP(h->alloc(&h->dL, nn)); GE_HIP(h->alloc(&h->dW, nn));
+        const int blocks = (int)std::min<int64_t>((N + 255) / 256, 8192);
+        hipLaunchKernelGGL(k_cost_terms, dim3(blocks), dim3(256), 0, h->stream, h->dX, N, h->cfg.cost, h->cfg.xmax, h->dL, h->dW);
+    }
+    GE_HIP(hipStreamSynchronize(h->stream));
+    return GE_OK;
+}
+
+ge_status init_permutation(ge_glove *h) {
+    const int64_t N = h->cfg.nnz;
+    GE_HIP(h->alloc(&h->dperm, (size_t)std::max<int64_t>(N, 1)));
+    h->perm.resize((size_t)N);
+    for (int64_t k = 0; k < N; ++k) h->perm[(size_t)k] = (int32_t)k;     // Permutation ctor
+    return GE_OK;
+}
+
+// Accumulators, then the parameters in the reference's draw order, straight into the final layout; the context side covers all V
+// rows, the focus side only the owned rows (same values a single-GPU run would hold there).
+ge_status init_state(ge_glove *h) {
+    const int32_t V = h->cfg.vocab_size, D = h->cfg.dim, rb = h->cfg.row_begin;
+    const uint64_t s0 = ge::JavaRandom::scramble(h->cfg.seed);
+    if (h->emb16) {
+        GE_HIP(h->alloc(&h->dhub_index, (size_t)V));
+        GE_HIP(hipMemcpyAsync(h->dhub_index, h->host_hub_index.data(), sizeof(int32_t) * (size_t)V, hipMemcpyHostToDevice, h->stream));
+        GE_HIP(h->alloc(&h->hub32, (size_t)std::max<int64_t>((int64_t)h->n_hub * D, 1)));
+    }
+    // Adagrad ctor: gradSq = 1 (Adagrad.java:27-33); Adam / AMSGrad ctors: every moment = 0 (new float[]).  Before the parameter
+    // init: a bf16 handle's bias lives in the accumulator row and must survive the fill.
+    const float v0 = h->moments() ? 0.0f : 1.0f;
+    for (int t : {GE_STATE_GSQ_FOCUS, GE_STATE_GSQ_CONTEXT, GE_STATE_M2_FOCUS, GE_STATE_M2_CONTEXT}) {
+        if (!h->tab[t]) continue;
+        const int64_t nr = h->tab_count[t] / D;
+        const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((nr * h->rw + 255) / 256, 8192));
+        hipLaunchKernelGGL(k_fill_rows, dim3(blocks), dim3(256), 0, h->stream, h->tab[t], nr, (int64_t)h->ds, h->fat ? D + 1 : D, h->rw, v0);
+    }
+    for (int t : {GE_STATE_GSQ_FBIAS, GE_STATE_GSQ_CBIAS, GE_STATE_M2_FBIAS, GE_STATE_M2_CBIAS}) {
+        if (!h->tab[t]) continue;
+        const int64_t n = h->tab_count[t];
+        hipLaunchKernelGGL(k_fill, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 4096))), dim3(256), 0, h->stream, h->tab[t], n, v0);
+    }
+    const TableView foc = view_of(h, GE_STATE_FOCUS), ctx = view_of(h, GE_STATE_CONTEXT);
+    const TableView fb = view_of(h, GE_STATE_FBIAS), cb = view_of(h, GE_STATE_CBIAS);
+    const int32_t bias_col = (h->fat && !h->emb16) ? D : -1;        // fp32 fat rows: the bias is a column of the row being written
+    auto launch = [&](void *f, void *c, int32_t row0, int32_t nrows) {          // hub_index / hub32: null unless bf16
+        hipLaunchKernelGGL(h->emb16 ? k_init_java<true> : k_init_java<false>, dim3((unsigned)((nrows + 127) / 128)), dim3(128), 0, h->stream,
+                           f, c, fb.first(), cb.first(), fb.stride, rb, row0, nrows, D, foc.stride, bias_col, h->rw, s0,
+                           (const int32_t *)h->dhub_index, h->hub32);
+    };
+    if (h->rows == V) launch(foc.base, ctx.base, 0, V);
+    else { launch(nullptr, ctx.base, 0, V); launch(foc.base, nullptr, rb, h->rows); }
+    GE_HIP(hipGetLastError());
+    GE_HIP(hipStreamSynchronize(h->stream));
+    h->rng.s = ge::JavaRandom::jump(s0, (uint64_t)V * (uint64_t)(2 + 2 * D));
+    return GE_OK;
+}
+
+ge_status ge_glove_create_impl(const ge_glove_cfg *cfg, const int32_t *I, const int32_t *J, const float *X, ge_glove **out) {
+    if (!out) return ge::fail(GE_ERR_ARG, "out is null");
+    *out = nullptr;
+    int32_t rb = 0, re = 0;
+    GE_CHECK(validate_config(cfg, I, J, X, &rb, &re));
+    GE_CHECK(ge::select_device(cfg->device));
+
+    std::unique_ptr<ge_glove, decltype(&ge_glove_destroy)> h(new (std::nothrow) ge_glove(), ge_glove_destroy);   // a failure below frees what the handle owns so far
+    if (!h) return ge::fail(GE_ERR_OOM, "host allocation failed");
+    h->cfg = *cfg;
+    h->cfg.row_begin = rb; h->cfg.row_end = re;
+    h->rows = re - rb;
+    h->stream = (hipStream_t)cfg->stream;
+    GE_CHECK(plan_geometry(h.get()));
+
+    CreateClock clk{std::getenv("GE_GLOVE_TIMING") != nullptr, h->stream};
+    hipDeviceProp_t prop;
+    GE_HIP(hipGetDeviceProperties(&prop, cfg->device));
+    h->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    GE_HIP(hipEventCreate(&h->ev0));
+    GE_HIP(hipEventCreate(&h->ev1));
+
+    GE_CHECK(alloc_tables(h.get()));
+    clk.lap("tables (placement search)");
+    GE_HIP(h->alloc(&h->dcost, 2));
+    GE_HIP(h->alloc(&h->djob, (size_t)cfg->threads));
+    if (h->hogwild()) {
+        plan_workers(h.get());
+        GE_CHECK(plan_epoch_layout(h.get(), I, J, X));
+    }
+    clk.lap("epoch layout");
+    if (!h->blocked) GE_CHECK(upload_nonzeros(h.get(), I, J, X));
+    if (cfg->shuffle == GE_SHUFFLE_JAVA) GE_CHECK(init_permutation(h.get()));
+    GE_CHECK(init_state(h.get()));
+    clk.lap("init and the rest");
+    *out = h.release();
+    return GE_OK;
+}
+
+// start of a Hogwild epoch on the handle's stream: cost accumulator and ticket counter zeroed, ev0 behind them
+ge_status begin_hogwild_epoch(ge_glove *h) {
+    GE_HIP(hipMemsetAsync(h->dcost, 0, 2 * sizeof(double), h->stream));
+    GE_HIP(hipEventRecord(h->ev0, h->stream));
+    h->last_launches = 0;
+    return GE_OK;
+}
+void launch_hogwild(ge_glove *h, const GloveParams &p, int blocks) {
+    hipLaunchKernelGGL(h->hw.fn, dim3((unsigned)blocks), dim3(256), 0, h->stream, p, (int32_t)h->hw_workers);
+    ++h->last_launches;
+}
+
+ge_status ge_glove_epoch_impl(ge_glove *h, int32_t iteration, double *cost_sum) {
+    GE_CHECK(check_handle(h));
     const int64_t N = h->cfg.nnz;
     if (h->cfg.shuffle == GE_SHUFFLE_JAVA && N > 0) {
         // ExtendedRandom.shuffle(int[]), cumulative on the same array (J/util/rnd/ExtendedRandom.java:398-407)
@@ -1463,11 +1590,10 @@ static ge_status ge_glove_epoch_impl(ge_glove *h, int32_t iteration, double *cos
     }
     GloveParams p;
     fill_params(h, p, iteration);
-    double total = 0.0;
-    h->last_launches = 0;
-    if (h->cfg.mode == GE_MODE_DETERMINISTIC) {
-        const int T = h->cfg.threads;
+    const int T = h->cfg.mode == GE_MODE_DETERMINISTIC ? h->cfg.threads : 0;
+    if (T > 0) {
         const int64_t per = N / T;
+        h->last_launches = 0;
         GE_HIP(hipMemsetAsync(h->djob, 0, sizeof(float) * (size_t)T, h->stream));
         GE_HIP(hipEventRecord(h->ev0, h->stream));
         for (int t = 0; t < T; ++t) {
@@ -1478,214 +1604,24 @@ static ge_status ge_glove_epoch_impl(ge_glove *h, int32_t iteration, double *cos
                                p, off, off + lines, h->djob + t);
             ++h->last_launches;
         }
-        GE_HIP(hipEventRecord(h->ev1, h->stream));
-        GE_HIP(hipGetLastError());
-        std::vector<float> jc((size_t)T);
-        GE_HIP(hipMemcpyAsync(jc.data(), h->djob, sizeof(float) * (size_t)T, hipMemcpyDeviceToHost, h->stream));
-        GE_HIP(hipStreamSynchronize(h->stream));
-        for (int t = 0; t < T; ++t) total += (double)jc[(size_t)t];       // localCost += job result (Optimizer.java:89)
     } else {
-        GE_HIP(hipMemsetAsync(h->dcost, 0, 2 * sizeof(double), h->stream));
-        GE_HIP(hipEventRecord(h->ev0, h->stream));
-        if (N > 0) {
-            hipLaunchKernelGGL(h->hw_fn, dim3(h->hw_blocks), dim3(256), 0, h->stream, p, (int32_t)h->hw_workers);
-            ++h->last_launches;
-        }
-        GE_HIP(hipEventRecord(h->ev1, h->stream));
-        GE_HIP(hipGetLastError());
-        GE_HIP(hipMemcpyAsync(&total, h->dcost, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        GE_HIP(hipStreamSynchronize(h->stream));
+        GE_CHECK(begin_hogwild_epoch(h));
+        if (N > 0) launch_hogwild(h, p, h->hw_blocks);
     }
+    GE_HIP(hipEventRecord(h->ev1, h->stream));
+    GE_HIP(hipGetLastError());
+    double total = 0.0;
+    std::vector<float> jc((size_t)T);                                     // deterministic: one fp32 cost per job
+    if (T > 0) GE_HIP(hipMemcpyAsync(jc.data(), h->djob, sizeof(float) * (size_t)T, hipMemcpyDeviceToHost, h->stream));
+    else GE_HIP(hipMemcpyAsync(&total, h->dcost, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    GE_HIP(hipStreamSynchronize(h->stream));
+    for (float c : jc) total += (double)c;                                // localCost += job result (Optimizer.java:89)
     GE_HIP(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
     if (cost_sum) *cost_sum = total;
     return GE_OK;
 }
 
-// bf16 build: an fp32 device copy of FOCUS or CONTEXT as the caller sees it (hub rows from their fp32 masters)
-// fat build: any table as the API shows it (rows [n x D] or a bias vector [n]) gathered out of the fat rows
-// does the API view of table `which` differ from how the handle stores it?  (fat rows: every fp32 table; interleaved
-// records: the row tables; bf16: the two embedding tables)
-static bool stored_strided(const ge_glove *h, int which) {
-    if (h->emb16 && (which == GE_STATE_FOCUS || which == GE_STATE_CONTEXT)) return false;     // bf16: converted, not gathered
-    return is_bias_table(which) ? h->fat : h->ds != h->cfg.dim;
-}
-static ge_status materialize_f32(ge_glove *h, int which, float **out) {
-    const int64_t n = h->tab_count[which];
-    float *d = nullptr;
-    GE_HIP(hipMalloc((void **)&d, sizeof(float) * (size_t)std::max<int64_t>(n, 1)));
-    if (stored_strided(h, which)) {
-        const Home hm = home_of(h, which);
-        hipLaunchKernelGGL(k_fat_gather, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 16384))), dim3(256), 0, h->stream,
-                           hm.base, n / hm.ncols, (int32_t)hm.stride, hm.col0, hm.ncols, d);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { (void)hipFree(d); return ge::fail(GE_ERR_HIP, "row gather failed: %s", hipGetErrorString(e)); }
-        *out = d;
-        return GE_OK;
-    }
-    hipLaunchKernelGGL(k_bf16_to_f32, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 8192)), dim3(256), 0, h->stream,
-                       reinterpret_cast<const uint16_t *>(h->tab[which]), d, n, h->cfg.dim, (int64_t)h->es);
-    if (which == GE_STATE_CONTEXT && h->n_hub > 0)
-        hipLaunchKernelGGL(k_hub_rows, dim3((unsigned)h->cfg.vocab_size), dim3(64), 0, h->stream, d, h->hub32, h->dhub_index, h->cfg.vocab_size, h->cfg.dim, 1);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { (void)hipFree(d); return ge::fail(GE_ERR_HIP, "bf16 -> fp32 conversion failed: %s", hipGetErrorString(e)); }
-    *out = d;
-    return GE_OK;
-}
-
-// (focus + context) / 2 of every row in a fresh device buffer (the caller frees it), enqueued on the handle's stream.
-static ge_status extract_to_device(ge_glove *h, bool f64, void **out) {
-    ge_status st = check_handle(h);
-    if (st != GE_OK) return st;
-    if (h->rows != h->cfg.vocab_size)
-        return ge::fail(GE_ERR_STATE, "extract needs all focus rows on this handle (owned [%d,%d) of %d); gather shards first",
-                        h->cfg.row_begin, h->cfg.row_end, h->cfg.vocab_size);
-    const int64_t n = (int64_t)h->cfg.vocab_size * h->cfg.dim;
-    const size_t bytes = (size_t)n * (f64 ? sizeof(double) : sizeof(float));
-    void *d = nullptr;
-    GE_HIP(hipMalloc(&d, bytes));
-    const int blocks = (int)std::min<int64_t>((n + 255) / 256, 8192);
-    float *foc = h->tab[GE_STATE_FOCUS], *ctx = h->tab[GE_STATE_CONTEXT];
-    const bool temp = h->emb16 || stored_strided(h, GE_STATE_FOCUS);
-    if (temp) {
-        foc = ctx = nullptr;
-        ge_status s1 = materialize_f32(h, GE_STATE_FOCUS, &foc);
-        ge_status s2 = s1 == GE_OK ? materialize_f32(h, GE_STATE_CONTEXT, &ctx) : s1;
-        if (s2 != GE_OK) { if (foc) (void)hipFree(foc); (void)hipFree(d); return s2; }
-    }
-    if (f64) hipLaunchKernelGGL(k_extract<double>, dim3(blocks), dim3(256), 0, h->stream, foc, ctx, (double *)d, n);
-    else     hipLaunchKernelGGL(k_extract<float>,  dim3(blocks), dim3(256), 0, h->stream, foc, ctx, (float *)d, n);
-    hipError_t e = hipGetLastError();
-    if (temp) {                                   // the temporaries may go once the kernel that reads them has run
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        (void)hipFree(foc); (void)hipFree(ctx);
-    }
-    if (e != hipSuccess) { (void)hipFree(d); return ge::fail(GE_ERR_HIP, "extract failed: %s", hipGetErrorString(e)); }
-    *out = d;
-    return GE_OK;
-}
-
-static ge_status extract_impl(ge_glove *h, void *out, bool f64) {
-    if (h && !out) return ge::fail(GE_ERR_ARG, "out is null");
-    void *d = nullptr;
-    ge_status st = extract_to_device(h, f64, &d);
-    if (st != GE_OK) return st;
-    const size_t bytes = (size_t)h->cfg.vocab_size * (size_t)h->cfg.dim * (f64 ? sizeof(double) : sizeof(float));
-    hipError_t e = hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(d);
-    if (e != hipSuccess) return ge::fail(GE_ERR_HIP, "extract copy failed: %s", hipGetErrorString(e));
-    return GE_OK;
-}
-ge_status ge_glove_extract_f32(ge_glove *h, float *out) { return extract_impl(h, out, false); }
-ge_status ge_glove_extract_f64(ge_glove *h, double *out) { return extract_impl(h, out, true); }
-
-ge_status ge_glove_get_state(ge_glove *h, int32_t which, float *out, int64_t count) {
-    ge_status st = check_handle(h);
-    if (st != GE_OK) return st;
-    if (which < 0 || which >= GE_STATE_COUNT || !out) return ge::fail(GE_ERR_ARG, "invalid state id %d or null buffer", which);
-    if (count != h->tab_count[which]) return ge::fail(GE_ERR_ARG, "state %d holds %lld floats, caller passed %lld", which, (long long)h->tab_count[which], (long long)count);
-    if (h->tab_count[which] == 0) return GE_OK;
-    if (stored_strided(h, which) || (h->emb16 && (which == GE_STATE_FOCUS || which == GE_STATE_CONTEXT))) {
-        float *d = nullptr;
-        st = materialize_f32(h, which, &d);
-        if (st != GE_OK) return st;
-        hipError_t e = hipMemcpyAsync(out, d, sizeof(float) * (size_t)count, hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        (void)hipFree(d);
-        if (e != hipSuccess) return ge::fail(GE_ERR_HIP, "state copy failed: %s", hipGetErrorString(e));
-        return GE_OK;
-    }
-    GE_HIP(hipMemcpyAsync(out, h->tab[which], sizeof(float) * (size_t)count, hipMemcpyDeviceToHost, h->stream));
-    GE_HIP(hipStreamSynchronize(h->stream));
-    return GE_OK;
-}
-
-ge_status ge_glove_set_state(ge_glove *h, int32_t which, const float *in, int64_t count) {
-    ge_status st = check_handle(h);
-    if (st != GE_OK) return st;
-    if (which < 0 || which >= GE_STATE_COUNT || !in) return ge::fail(GE_ERR_ARG, "invalid state id %d or null buffer", which);
-    if (count != h->tab_count[which]) return ge::fail(GE_ERR_ARG, "state %d holds %lld floats, caller passed %lld", which, (long long)h->tab_count[which], (long long)count);
-    if (count == 0) return GE_OK;
-    if (stored_strided(h, which)) {
-        float *d = nullptr;
-        GE_HIP(hipMalloc((void **)&d, sizeof(float) * (size_t)count));
-        hipError_t e = hipMemcpyAsync(d, in, sizeof(float) * (size_t)count, hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess) {
-            const Home hm = home_of(h, which);
-            hipLaunchKernelGGL(k_fat_scatter, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((count + 255) / 256, 16384))), dim3(256), 0, h->stream,
-                               hm.base, count / hm.ncols, (int32_t)hm.stride, hm.col0, hm.ncols, d);
-            e = hipGetLastError();
-            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        }
-        (void)hipFree(d);
-        if (e != hipSuccess) return ge::fail(GE_ERR_HIP, "state copy failed: %s", hipGetErrorString(e));
-        return GE_OK;
-    }
-    if (h->emb16 && (which == GE_STATE_FOCUS || which == GE_STATE_CONTEXT)) {
-        float *d = nullptr;
-        GE_HIP(hipMalloc((void **)&d, sizeof(float) * (size_t)std::max<int64_t>(count, 1)));
-        hipError_t e = hipMemcpyAsync(d, in, sizeof(float) * (size_t)count, hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess) {
-            if (which == GE_STATE_CONTEXT && h->n_hub > 0)
-                hipLaunchKernelGGL(k_hub_rows, dim3((unsigned)h->cfg.vocab_size), dim3(64), 0, h->stream, d, h->hub32, h->dhub_index, h->cfg.vocab_size, h->cfg.dim, 0);
-            hipLaunchKernelGGL(k_f32_to_bf16, dim3((unsigned)std::min<int64_t>((count + 255) / 256, 8192)), dim3(256), 0, h->stream,
-                               d, reinterpret_cast<uint16_t *>(h->tab[which]), count, h->cfg.dim, (int64_t)h->es);
-            e = hipStreamSynchronize(h->stream);
-        }
-        (void)hipFree(d);
-        if (e != hipSuccess) return ge::fail(GE_ERR_HIP, "state copy failed: %s", hipGetErrorString(e));
-        return GE_OK;
-    }
-    GE_HIP(hipMemcpyAsync(h->tab[which], in, sizeof(float) * (size_t)count, hipMemcpyHostToDevice, h->stream));
-    GE_HIP(hipStreamSynchronize(h->stream));
-    return GE_OK;
-}
-
-ge_status ge_glove_device_ptr(ge_glove *h, int32_t which, void **dptr, int64_t *count) {
-    if (!h) return ge::fail(GE_ERR_ARG, "null ge_glove handle");
-    if (which < 0 || which >= GE_STATE_COUNT || !dptr) return ge::fail(GE_ERR_ARG, "invalid state id %d or null out", which);
-    if (h->emb16 && (which == GE_STATE_FOCUS || which == GE_STATE_CONTEXT))
-        return ge::fail(GE_ERR_STATE, "table %d is stored as bf16 (+ fp32 hub rows); use ge_glove_get_state/set_state", which);
-    if (stored_strided(h, which)) {
-        // a row table is [n x row_stride]; a bias "table" is one column of its home table (home_of): the pointer is row 0's
-        // scalar, consecutive rows are row_stride floats apart.  *count = floats from the returned pointer to the end of the last row's part.
-        const Home hm = home_of(h, which);
-        *dptr = hm.base + hm.col0;
-        const int64_t nr = h->tab_count[which] / hm.ncols;
-        if (count) *count = nr > 0 ? (nr - 1) * hm.stride + (is_bias_table(which) ? 1 : h->rw) : 0;
-        return GE_OK;
-    }
-    *dptr = h->tab[which];
-    if (count) *count = h->tab_count[which];
-    return GE_OK;
-}
-
-ge_status ge_glove_context_layout(ge_glove *h, ge_context_layout *out) {
-    if (!h || !out) return ge::fail(GE_ERR_ARG, "null argument");
-    out->table = h->tab[GE_STATE_CONTEXT];
-    out->dtype = h->emb16 ? GE_DTYPE_BF16 : GE_DTYPE_F32;
-    out->hub_rows = h->emb16 ? h->hub32 : nullptr;
-    out->hub_index = h->emb16 ? h->dhub_index : nullptr;
-    out->n_hub = h->emb16 ? h->n_hub : 0;
-    out->vocab_size = h->cfg.vocab_size; out->dim = h->cfg.dim;
-    out->row_stride = h->emb16 ? h->es : h->ds;
-    out->accum = h->tab[GE_STATE_GSQ_CONTEXT];
-    out->accum_stride = h->ds;
-    const Home cb = home_of(h, GE_STATE_CBIAS), gcb = home_of(h, GE_STATE_GSQ_CBIAS);
-    out->bias = cb.base + cb.col0; out->bias_stride = (int32_t)cb.stride;
-    out->accum_bias = gcb.base + gcb.col0; out->accum_bias_stride = (int32_t)gcb.stride;
-    return GE_OK;
-}
-
-ge_status ge_glove_get_perm(ge_glove *h, int32_t *out, int64_t count) {
-    if (!h || !out) return ge::fail(GE_ERR_ARG, "null argument");
-    if (h->cfg.shuffle != GE_SHUFFLE_JAVA) return ge::fail(GE_ERR_STATE, "no permutation array unless shuffle == GE_SHUFFLE_JAVA");
-    if (count != h->cfg.nnz) return ge::fail(GE_ERR_ARG, "perm holds %lld entries", (long long)h->cfg.nnz);
-    std::memcpy(out, h->perm.data(), sizeof(int32_t) * (size_t)count);
-    return GE_OK;
-}
-
-static ge_status ge_glove_epoch_order_impl(ge_glove *h, int32_t iteration, int32_t *out, int64_t count) {
+ge_status ge_glove_epoch_order_impl(ge_glove *h, int32_t iteration, int32_t *out, int64_t count) {
     if (!h || !out) return ge::fail(GE_ERR_ARG, "null argument");
     if (h->cfg.mode != GE_MODE_HOGWILD) return ge::fail(GE_ERR_STATE, "epoch order is defined for GE_MODE_HOGWILD handles");
     const int64_t N = h->cfg.nnz;
@@ -1694,8 +1630,7 @@ static ge_status ge_glove_epoch_order_impl(ge_glove *h, int32_t iteration, int32
     fill_params(h, p, iteration);
     std::vector<int32_t> key, border, cstart;        // blocked layout: copied back from the device (a testing aid, not a hot path)
     if (h->blocked) {
-        ge_status st = check_handle(h);
-        if (st != GE_OK) return st;
+        GE_CHECK(check_handle(h));
         key.resize((size_t)std::max<int64_t>(N, 1)); border.resize(key.size()); cstart.resize((size_t)h->n_chunks + 1);
         if (N > 0) {
             GE_HIP(hipMemcpy(key.data(), h->lay.bA, sizeof(int32_t) * (size_t)N, hipMemcpyDeviceToHost));
@@ -1724,6 +1659,65 @@ static ge_status ge_glove_epoch_order_impl(ge_glove *h, int32_t iteration, int32
     return GE_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+void ge_glove_cfg_default(ge_glove_cfg *cfg) {
+    if (!cfg) return;
+    std::memset(cfg, 0, sizeof(*cfg));
+    cfg->cost = GE_COST_GLOVE;
+    cfg->opt = GE_OPT_ADAGRAD;
+    cfg->learning_rate = 0.05f;
+    cfg->threads = 1;
+    cfg->mode = GE_MODE_HOGWILD;
+    cfg->shuffle = GE_SHUFFLE_DEVICE;
+}
+
+ge_status ge_glove_extract_f32(ge_glove *h, float *out) { return extract_impl(h, out, false); }
+ge_status ge_glove_extract_f64(ge_glove *h, double *out) { return extract_impl(h, out, true); }
+ge_status ge_glove_get_state(ge_glove *h, int32_t which, float *out, int64_t count) { return state_io(h, which, out, count, TO_DENSE); }
+ge_status ge_glove_set_state(ge_glove *h, int32_t which, const float *in, int64_t count) { return state_io(h, which, const_cast<float *>(in), count, FROM_DENSE); }
+
+ge_status ge_glove_device_ptr(ge_glove *h, int32_t which, void **dptr, int64_t *count) {
+    if (!h) return ge::fail(GE_ERR_ARG, "null ge_glove handle");
+    if (which < 0 || which >= GE_STATE_COUNT || !dptr) return ge::fail(GE_ERR_ARG, "invalid state id %d or null out", which);
+    const TableView v = view_of(h, which);
+    if (v.bf16) return ge::fail(GE_ERR_STATE, "table %d is stored as bf16 (+ fp32 hub rows); use ge_glove_get_state/set_state", which);
+    // a row table is [n x row_stride]; a bias "table" may be one column of its home table (view_of): the pointer is row 0's scalar,
+    // consecutive rows are row_stride floats apart.  *count = floats from the returned pointer to the end of the last row's part.
+    *dptr = v.first();
+    const int64_t nr = h->tab_count[which] / v.ncols;
+    if (count) *count = nr > 0 ? (nr - 1) * v.stride + (is_bias_table(which) ? 1 : h->rw) : 0;
+    return GE_OK;
+}
+
+ge_status ge_glove_context_layout(ge_glove *h, ge_context_layout *out) {
+    if (!h || !out) return ge::fail(GE_ERR_ARG, "null argument");
+    const TableView ctx = view_of(h, GE_STATE_CONTEXT), acc = view_of(h, GE_STATE_GSQ_CONTEXT);
+    const TableView cb = view_of(h, GE_STATE_CBIAS), gcb = view_of(h, GE_STATE_GSQ_CBIAS);
+    out->table = ctx.base;
+    out->dtype = ctx.bf16 ? GE_DTYPE_BF16 : GE_DTYPE_F32;
+    out->hub_rows = ctx.bf16 ? h->hub32 : nullptr;
+    out->hub_index = ctx.bf16 ? h->dhub_index : nullptr;
+    out->n_hub = ctx.bf16 ? h->n_hub : 0;
+    out->vocab_size = h->cfg.vocab_size; out->dim = h->cfg.dim;
+    out->row_stride = (int32_t)ctx.stride;
+    out->accum = acc.base;
+    out->accum_stride = (int32_t)acc.stride;
+    out->bias = cb.first(); out->bias_stride = (int32_t)cb.stride;
+    out->accum_bias = gcb.first(); out->accum_bias_stride = (int32_t)gcb.stride;
+    return GE_OK;
+}
+
+ge_status ge_glove_get_perm(ge_glove *h, int32_t *out, int64_t count) {
+    if (!h || !out) return ge::fail(GE_ERR_ARG, "null argument");
+    if (h->cfg.shuffle != GE_SHUFFLE_JAVA) return ge::fail(GE_ERR_STATE, "no permutation array unless shuffle == GE_SHUFFLE_JAVA");
+    if (count != h->cfg.nnz) return ge::fail(GE_ERR_ARG, "perm holds %lld entries", (long long)h->cfg.nnz);
+    std::memcpy(out, h->perm.data(), sizeof(int32_t) * (size_t)count);
+    return GE_OK;
+}
+
 ge_status ge_glove_rng_state(ge_glove *h, uint64_t *state) {
     if (!h || !state) return ge::fail(GE_ERR_ARG, "null argument");
     *state = h->rng.s;
@@ -1740,7 +1734,7 @@ ge_status ge_glove_last_kernel_ms(ge_glove *h, float *ms, int32_t *launches) {
 ge_status ge_glove_get_info(ge_glove *h, ge_glove_info *info) {
     if (!h || !info) return ge::fail(GE_ERR_ARG, "null argument");
     std::memset(info, 0, sizeof(*info));
-    info->group_width = 64; info->vector_width = h->hw_vw; info->chunks_per_lane = h->hw_nch;
+    info->group_width = 64; info->vector_width = h->hw.vw; info->chunks_per_lane = h->hw.nch;
     info->blocks = h->cfg.mode == GE_MODE_HOGWILD ? h->hw_blocks : 1;
     info->groups_in_flight = h->cfg.mode == GE_MODE_HOGWILD ? h->hw_workers : 1;
     info->hot_columns = h->hot_cols; info->hot_nonzeros = h->hot_nnz; info->hot_threshold = h->hot_threshold;
@@ -1761,26 +1755,16 @@ ge_status ge_glove_get_info(ge_glove *h, ge_glove_info *info) {
 
 }  // extern "C"
 namespace ge {
-// What ge_glove_extract_f32 returns, left on the device (pca.hip fits and projects it there): a fresh buffer of V x D floats,
-// complete when this returns; the caller frees it.
 ge_status glove_extract_device_f32(ge_glove *h, float **rows, int32_t *vocab_size, int32_t *dim, int32_t *device) {
-    void *d = nullptr;
-    ge_status st = extract_to_device(h, false, &d);
-    if (st != GE_OK) return st;
+    DeviceBuf d;
+    GE_CHECK(extract_to_device(h, false, &d.p));
     hipError_t e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) { (void)hipFree(d); return ge::fail(GE_ERR_HIP, "extract failed: %s", hipGetErrorString(e)); }
-    *rows = (float *)d; *vocab_size = h->cfg.vocab_size; *dim = h->cfg.dim; *device = h->cfg.device;
+    if (e != hipSuccess) return hip_failed("extract", e);
+    *rows = static_cast<float *>(d.release()); *vocab_size = h->cfg.vocab_size; *dim = h->cfg.dim; *device = h->cfg.device;
     return GE_OK;
 }
-// A Hogwild epoch in `nseg` launches (ge_sync_epoch: the hub rows of a sharded run are reconciled between them).  The chunks of
-// the epoch are handed out by ticket through a keyed bijection, so tickets [n seg / nseg, n (seg + 1) / nseg) are a random nseg-th
-// of the epoch; the cost accumulates on the device over the segments.  Nothing here blocks the host: glove_epoch_finish does.
-// leave_blocks: workgroups NOT launched (their wavefront slots stay free for kernels running beside the epoch: the live hub-row exchange
-// of a sharded run); after_reset: recorded once the ticket counter holds this segment's first ticket (a host that watches the counter
-// waits for it, so that it never reads the previous epoch's value).
 ge_status glove_epoch_segment(ge_glove *h, int32_t iteration, int32_t seg, int32_t nseg, int32_t leave_blocks, hipEvent_t after_reset) {
-    ge_status st = check_handle(h);
-    if (st != GE_OK) return st;
+    GE_CHECK(check_handle(h));
     if (h->cfg.mode != GE_MODE_HOGWILD || h->cfg.shuffle == GE_SHUFFLE_JAVA) return ge::fail(GE_ERR_STATE, "a segmented epoch needs a GE_MODE_HOGWILD handle with a device-side order");
     if (nseg < 1 || nseg > 64 || seg < 0 || seg >= nseg) return ge::fail(GE_ERR_ARG, "segment %d of %d", seg, nseg);
     GloveParams p;
@@ -1788,9 +1772,7 @@ ge_status glove_epoch_segment(ge_glove *h, int32_t iteration, int32_t seg, int32
     const int64_t n = h->cfg.nnz > 0 ? h->n_chunks : 0;
     const int64_t begin = n * seg / nseg, end = n * (seg + 1) / nseg;
     if (seg == 0) {
-        GE_HIP(hipMemsetAsync(h->dcost, 0, 2 * sizeof(double), h->stream));
-        GE_HIP(hipEventRecord(h->ev0, h->stream));
-        h->last_launches = 0;
+        GE_CHECK(begin_hogwild_epoch(h));
         h->seg_timed = 0;
     }
     if (end > begin) {
@@ -1801,31 +1783,26 @@ ge_status glove_epoch_segment(ge_glove *h, int32_t iteration, int32_t seg, int32
         hipEvent_t *ev = &h->seg_ev[2 * h->seg_timed];
         for (int k = 0; k < 2; ++k) if (!ev[k]) GE_HIP(hipEventCreate(&ev[k]));
         GE_HIP(hipEventRecord(ev[0], h->stream));
-        hipLaunchKernelGGL(h->hw_fn, dim3((unsigned)std::max(1, h->hw_blocks - std::max(0, leave_blocks))), dim3(256), 0, h->stream, p, (int32_t)h->hw_workers);
+        launch_hogwild(h, p, std::max(1, h->hw_blocks - std::max(0, leave_blocks)));
         GE_HIP(hipEventRecord(ev[1], h->stream));
         ++h->seg_timed;
-        ++h->last_launches;
         GE_HIP(hipGetLastError());
     }
     else if (after_reset) GE_HIP(hipEventRecord(after_reset, h->stream));
     if (seg == nseg - 1) GE_HIP(hipEventRecord(h->ev1, h->stream));
     return GE_OK;
 }
-// the epoch's ticket counter (device memory; tickets [0, *tickets) are the epoch's chunks) and the event behind the last launch
 ge_status glove_epoch_progress(ge_glove *h, const unsigned long long **counter, int64_t *tickets, hipEvent_t *done) {
-    ge_status st = check_handle(h);
-    if (st != GE_OK) return st;
+    GE_CHECK(check_handle(h));
     if (counter) *counter = reinterpret_cast<const unsigned long long *>(h->dcost + 1);
     if (tickets) *tickets = h->cfg.nnz > 0 ? h->n_chunks : 0;
     if (done) *done = h->ev1;
     return GE_OK;
 }
-// the columns this handle's epoch kernel treats as hubs (resident runs that publish the row and its accumulator row by float atomics)
 const std::vector<int32_t> *glove_kernel_hubs(const ge_glove *h) { return (h && h->blocked && h->cfg.hot_columns != GE_HOT_NONE) ? &h->lay.hubs : nullptr; }
 const std::vector<int32_t> *glove_hub_counts(const ge_glove *h) { return h ? &h->lay.heavy_count : nullptr; }
 ge_status glove_epoch_finish(ge_glove *h, double *cost_sum) {
-    ge_status st = check_handle(h);
-    if (st != GE_OK) return st;
+    GE_CHECK(check_handle(h));
     double total = 0.0;
     GE_HIP(hipMemcpyAsync(&total, h->dcost, sizeof(double), hipMemcpyDeviceToHost, h->stream));
     GE_HIP(hipStreamSynchronize(h->stream));
@@ -1835,9 +1812,7 @@ ge_status glove_epoch_finish(ge_glove *h, double *cost_sum) {
     if (cost_sum) *cost_sum = total;
     return GE_OK;
 }
-// the busy columns of this handle's shard (ascending; ge_layout.h `heavy`), for the small exchanges of a sharded run
 const std::vector<int32_t> *glove_hub_columns(const ge_glove *h) { return h ? &h->lay.heavy : nullptr; }
-// what sync.hip needs to know about a handle (struct ge_glove is private to this file)
 ge_status glove_sync_view(ge_glove *h, int32_t *opt, int32_t *mode, void **stream, int32_t *device) {
     if (!h) return ge::fail(GE_ERR_ARG, "null ge_glove handle");
     *opt = h->cfg.opt; *mode = h->cfg.mode; *stream = (void *)h->stream; *device = h->cfg.device;
@@ -1858,9 +1833,7 @@ void ge_glove_destroy(ge_glove *h) {
 }
 
 // ---- guarded entry points (bodies above allocate on the host) ----
-ge_status ge_glove_create(const ge_glove_cfg *cfg, const int32_t *I, const int32_t *J, const float *X, ge_glove **out) {
-    GE_GUARD(ge_glove_create_impl(cfg, I, J, X, out));
-}
+ge_status ge_glove_create(const ge_glove_cfg *cfg, const int32_t *I, const int32_t *J, const float *X, ge_glove **out) { GE_GUARD(ge_glove_create_impl(cfg, I, J, X, out)); }
 ge_status ge_glove_epoch(ge_glove *h, int32_t iteration, double *cost_sum) { GE_GUARD(ge_glove_epoch_impl(h, iteration, cost_sum)); }
 ge_status ge_glove_epoch_order(ge_glove *h, int32_t iteration, int32_t *out, int64_t count) { GE_GUARD(ge_glove_epoch_order_impl(h, iteration, out, count)); }
 

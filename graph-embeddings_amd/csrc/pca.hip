@@ -3,6 +3,7 @@
 // (k_pca_project, fp32 matrix cores).  The reference has no counterpart (it parses `pca:` and prints it); the semantics are
 // written down in include/geglove.h.
 #include "ge_common.h"
+#include "ge_glove_internal.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>

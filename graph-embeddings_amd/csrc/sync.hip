@@ -20,6 +20,7 @@
 // needs no RCCL), a local group (the C++ CLI rehearses N ranks inside one process) or three callbacks of the host (tests: gloo).
 // The wire / base buffers are DENSE [rows x cols] whatever the table's row stride (fat rows, interleaved records).
 #include "ge_common.h"
+#include "ge_glove_internal.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -33,17 +34,6 @@
 #include <thread>
 #include <chrono>
 #include <vector>
-
-// glove.hip
-namespace ge {
-ge_status glove_sync_view(ge_glove *h, int32_t *opt, int32_t *mode, void **stream, int32_t *device);
-ge_status glove_epoch_segment(ge_glove *h, int32_t iteration, int32_t seg, int32_t nseg, int32_t leave_blocks, hipEvent_t after_reset);
-ge_status glove_epoch_finish(ge_glove *h, double *cost_sum);
-ge_status glove_epoch_progress(ge_glove *h, const unsigned long long **counter, int64_t *tickets, hipEvent_t *done);
-const std::vector<int32_t> *glove_hub_columns(const ge_glove *h);
-const std::vector<int32_t> *glove_hub_counts(const ge_glove *h);
-const std::vector<int32_t> *glove_kernel_hubs(const ge_glove *h);
-}
 
 namespace {
 

@@ -37,7 +37,11 @@ SYMBOLS = (
     "ge_sim_cfg_default", "ge_sim_cfg_size", "ge_sim_pattern_supported", "ge_similarity_pairs", "ge_sim_pairs_get", "ge_sim_pairs_destroy", "ge_copy_bandwidth", "ge_last_error", "ge_version", "ge_glove_cfg_size", "ge_bca_cfg_size", "ge_device_count",
     "ge_pca_cfg_default", "ge_pca_cfg_size", "ge_pca_fit", "ge_glove_pca_fit", "ge_pca_from_moments", "ge_pca_get", "ge_pca_transform",
     "ge_glove_pca_transform", "ge_pca_last_kernel_ms", "ge_pca_destroy",
+    "ge_nn_cfg_default", "ge_nn_cfg_size", "ge_nn_create", "ge_glove_nn_create", "ge_nn_query_rows", "ge_nn_query_vectors", "ge_nn_get",
+    "ge_nn_last_kernel_ms", "ge_nn_destroy",
 )
+GE_NN_COSINE, GE_NN_DOT = 0, 1
+NN_METRICS = {"cosine": GE_NN_COSINE, "dot": GE_NN_DOT}
 
 
 class GloveCfg(C.Structure):
@@ -104,6 +108,10 @@ class SyncCfg(C.Structure):
 
 class PcaCfg(C.Structure):
     _fields_ = [("variance", C.c_double), ("max_components", C.c_int32), ("device", C.c_int32), ("stream", C.c_void_p)]
+
+
+class NnCfg(C.Structure):
+    _fields_ = [("metric", C.c_int32), ("device", C.c_int32), ("stream", C.c_void_p)]
 
 
 class GeError(RuntimeError):
@@ -208,6 +216,7 @@ def lib():
         raise ImportError("libgeglove.so was built from another revision of include/geglove.h (ge_glove_cfg is %d bytes there, "
                           "%d here): rebuild with `make -C graph-embeddings_amd/csrc`" % (L.ge_glove_cfg_size(), C.sizeof(GloveCfg)))
     _declare_pca(L)
+    _declare_nn(L)
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int:      # default restype -> ge_status
@@ -310,6 +319,109 @@ class Pca:
     def close(self):
         if self._h:
             lib().ge_pca_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _declare_nn(L):
+    """The nearest-neighbour section of include/geglove.h."""
+    vp, i32p, f32p = C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float)
+    L.ge_nn_cfg_default.argtypes = [C.POINTER(NnCfg)]; L.ge_nn_cfg_default.restype = None
+    L.ge_nn_cfg_size.argtypes = []; L.ge_nn_cfg_size.restype = C.c_int32
+    if L.ge_nn_cfg_size() != C.sizeof(NnCfg):
+        raise ImportError("libgeglove.so was built from another revision of include/geglove.h (ge_nn_cfg is %d bytes there, %d here): "
+                          "rebuild with `make -C graph-embeddings_amd/csrc`" % (L.ge_nn_cfg_size(), C.sizeof(NnCfg)))
+    L.ge_nn_create.argtypes = [f32p, C.c_int64, C.c_int32, i32p, C.c_int64, C.POINTER(NnCfg), C.POINTER(vp)]
+    L.ge_glove_nn_create.argtypes = [vp, i32p, C.c_int64, C.POINTER(NnCfg), C.POINTER(vp)]
+    L.ge_nn_query_rows.argtypes = [vp, i32p, C.c_int64, C.c_int32, C.c_int32, i32p, f32p]
+    L.ge_nn_query_vectors.argtypes = [vp, f32p, C.c_int64, C.c_int32, i32p, f32p]
+    L.ge_nn_get.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.ge_nn_last_kernel_ms.argtypes = [vp, f32p, f32p]
+    L.ge_nn_destroy.argtypes = [vp]; L.ge_nn_destroy.restype = None
+
+
+class Neighbors:
+    """A ge_nn index: Neighbors.create(rows) / Neighbors.create_glove(handle), then query_rows(ids, k) / query_vectors(vectors, k),
+    each returning (int32[nq, k] original row ids, float32[nq, k] scores), best first."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @staticmethod
+    def _cfg(metric, device):
+        cfg = NnCfg(); lib().ge_nn_cfg_default(C.byref(cfg))
+        cfg.metric, cfg.device = NN_METRICS.get(metric, metric), device
+        return cfg
+
+    @staticmethod
+    def _subset(subset):
+        import numpy as np
+        if subset is None:
+            return None, None, 0
+        subset = np.ascontiguousarray(subset, dtype=np.int32)
+        return subset, subset.ctypes.data_as(C.POINTER(C.c_int32)), subset.shape[0]
+
+    @classmethod
+    def create(cls, rows, subset=None, metric="cosine", device=0):
+        import numpy as np
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        keep, sub, n_sub = cls._subset(subset)
+        h = C.c_void_p()
+        check(lib().ge_nn_create(rows.ctypes.data_as(C.POINTER(C.c_float)), rows.shape[0], rows.shape[1], sub, n_sub,
+                                 C.byref(cls._cfg(metric, device)), C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def create_glove(cls, glove_handle, subset=None, metric="cosine"):
+        keep, sub, n_sub = cls._subset(subset)
+        h = C.c_void_p()
+        check(lib().ge_glove_nn_create(glove_handle, sub, n_sub, C.byref(cls._cfg(metric, 0)), C.byref(h)))
+        return cls(h)
+
+    def get(self):
+        """(n_indexed, dim, metric)"""
+        n, dim, metric = C.c_int64(), C.c_int32(), C.c_int32()
+        check(lib().ge_nn_get(self._h, C.byref(n), C.byref(dim), C.byref(metric)))
+        return n.value, dim.value, metric.value
+
+    @staticmethod
+    def _out(nq, k):
+        import numpy as np
+        idx = np.empty((nq, k), dtype=np.int32); score = np.empty((nq, k), dtype=np.float32)
+        return idx, score, idx.ctypes.data_as(C.POINTER(C.c_int32)), score.ctypes.data_as(C.POINTER(C.c_float))
+
+    def query_rows(self, query_ids, k, exclude_self=False):
+        """query_ids: None (every indexed row, in order) or row ids that are members of the index."""
+        import numpy as np
+        if query_ids is None:
+            ids, nq = None, self.get()[0]
+        else:
+            keep = np.ascontiguousarray(query_ids, dtype=np.int32)
+            ids, nq = keep.ctypes.data_as(C.POINTER(C.c_int32)), keep.shape[0]
+        idx, score, pi, ps = self._out(nq, k)
+        check(lib().ge_nn_query_rows(self._h, ids, nq, k, 1 if exclude_self else 0, pi, ps))
+        return idx, score
+
+    def query_vectors(self, vectors, k):
+        import numpy as np
+        vectors = np.ascontiguousarray(vectors, dtype=np.float32)
+        idx, score, pi, ps = self._out(vectors.shape[0], k)
+        check(lib().ge_nn_query_vectors(self._h, vectors.ctypes.data_as(C.POINTER(C.c_float)), vectors.shape[0], k, pi, ps))
+        return idx, score
+
+    def kernel_ms(self):
+        prep, query = C.c_float(), C.c_float()
+        check(lib().ge_nn_last_kernel_ms(self._h, C.byref(prep), C.byref(query)))
+        return prep.value, query.value
+
+    def close(self):
+        if self._h:
+            lib().ge_nn_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -257,7 +257,9 @@ struct Configuration {
              // multi-GPU: gpus ranks, one thread each, rows sharded, context exchanged through ge_sync
              int gpus = 1, accum_every = 0, hub_segments = 0; std::string exchange = "overlap", transport = "auto", wire = "bf16";
              // off | apply: reduce the trained vectors to the leading components the `pca:` block asks for before they are written
-             std::string pca = "off"; } device;
+             std::string pca = "off";
+             // K > 0: after the vectors, write the K nearest kept vertices of every kept vertex to <name>.neighbors.tsv; cosine | dot
+             int neighbors = 0; std::string neighbors_metric = "cosine"; } device;
     std::vector<std::string> ignored_keys;     // legacy keys of the shipped YAMLs that the bean does not know
 
     int getThreads() const {       // Configuration.java:71-73
@@ -268,6 +270,7 @@ struct Configuration {
     std::string getNormalize() const { return bca.normalize.empty() ? "none" : bca.normalize; }
     bool usingPca() const { return pca.present; }
     bool applyingPca() const { return device.pca == "apply"; }
+    bool writingNeighbors() const { return device.neighbors > 0; }
     bool usingWeights() const { return has_weights && !weights.empty(); }
     bool usingSimilarity() const { return !similarity.empty(); }
 
@@ -347,6 +350,8 @@ struct Configuration {
                     else if (q.first == "load_coo") c.device.load_coo = q.second.scalar;
                     else if (q.first == "gpus") c.device.gpus = std::max(1, (int)num(&q.second));
                     else if (q.first == "pca") c.device.pca = q.second.scalar;
+                    else if (q.first == "neighbors") c.device.neighbors = (int)num(&q.second);
+                    else if (q.first == "neighbors_metric") c.device.neighbors_metric = q.second.scalar;
                     else if (q.first == "exchange") c.device.exchange = q.second.scalar;        // overlap | sync
                     else if (q.first == "transport") c.device.transport = q.second.scalar;      // auto | rccl | host
                     else if (q.first == "wire") c.device.wire = q.second.scalar;                // bf16 | f32
@@ -387,6 +392,8 @@ struct Configuration {
         if (c.device.pca != "off" && c.device.pca != "apply") throw InvalidConfigurationException("Invalid device.pca, choose one of: off, apply");
         if (c.applyingPca() && !c.usingPca()) throw InvalidConfigurationException("device.pca: apply needs a pca block with a variance");
         if (c.applyingPca() && !(c.pca.variance > 0 && c.pca.variance <= 1)) throw InvalidConfigurationException("Invalid PCA parameters, variance must lie in (0, 1]");
+        if (c.device.neighbors < 0 || c.device.neighbors > 128) throw InvalidConfigurationException("Invalid device.neighbors, choose a number from 1 to 128 (0 = off)");
+        if (c.device.neighbors_metric != "cosine" && c.device.neighbors_metric != "dot") throw InvalidConfigurationException("Invalid device.neighbors_metric, choose one of: cosine, dot");
     }
 
     static std::string similarity_to_string(const std::map<std::string, std::string> &m) {     // SimilarityGroup.toString
@@ -426,6 +433,7 @@ struct Configuration {
             L.push_back("Using the following similarity metrics:");
             for (auto &s : similarity) L.push_back(similarity_to_string(s));
         } else L.push_back("No similarity matching will be performed");
+        if (writingNeighbors()) L.push_back("Nearest neighbours: " + std::to_string(device.neighbors) + " (" + device.neighbors_metric + ")");
         return L;
     }
 };
@@ -1137,15 +1145,89 @@ inline std::string applyPca(const Configuration &config, Optimum &optimum, int V
     return b;
 }
 
+// Which vertices are written (type switch, then the prefix filter of that type: EmbeddingTextWriter.java:100-131), in order.
+inline std::vector<int> keptVertices(const Configuration &config, const CoOccurrenceMatrix &m) {
+    const bool write[3] = {config.output.has_uri, config.output.has_blank, config.output.has_literal};
+    std::vector<int> keep;
+    const int V = m.vocabSize();
+    for (int i = 0; i < V; ++i) {
+        const int8_t type = m.getType(i);
+        if (!write[type]) continue;
+        const std::vector<std::string> &pre = type == URI ? config.output.uri : type == BLANK ? config.output.blank : config.output.literal;
+        if (!pre.empty()) {
+            const std::string key = m.getKey(i);
+            bool any = false;
+            for (auto &p : pre) if (key.compare(0, p.size(), p) == 0) { any = true; break; }
+            if (!any) continue;
+        }
+        keep.push_back(i);
+    }
+    return keep;
+}
+
+// `device: { neighbors: K }`: the K nearest kept vertices of every kept vertex, from the final result (after `device.pca: apply`),
+// on device.id, once -- also after a multi-GPU run (the result is replicated).  <fileName>.neighbors.tsv carries the banner, then
+// one line per kept vertex in dict order: its 0-based position in the dict file, then K pairs position<TAB>score, best first,
+// scores in the number format of the vectors file.  `warning` is set when fewer than K + 1 vertices are kept and K shrinks;
+// returns the line Main logs.
+inline std::string writeNeighbors(const Configuration &config, const Optimum &optimum, const CoOccurrenceMatrix &m, const std::string &fileName,
+                                  const std::string &outputFolder, std::string &warning) {
+    if (ge_nn_cfg_size() != (int32_t)sizeof(ge_nn_cfg))
+        throw std::runtime_error("libgeglove.so and this host were built from different revisions of include/geglove.h; rebuild both");
+    const int V = m.vocabSize();
+    if (V < 1 || optimum.result.size() % (size_t)V != 0) throw std::runtime_error("neighbors: the result is not a table of V rows");
+    const int D = (int)(optimum.result.size() / (size_t)V);
+    const std::vector<int> keep = keptVertices(config, m);
+    const long long kept = (long long)keep.size();
+    int K = config.device.neighbors;
+    if (kept < (long long)K + 1) {
+        K = (int)std::max(0LL, kept - 1);
+        warning = "only " + std::to_string(kept) + " vertices are written: listing " + std::to_string(K) + " neighbours instead of " +
+                  std::to_string(config.device.neighbors);
+    }
+    std::vector<int32_t> index((size_t)kept * (size_t)K);
+    std::vector<float> score((size_t)kept * (size_t)K);
+    if (K > 0) {
+        std::vector<float> rows(optimum.result.begin(), optimum.result.end());      // widened fp32 values: exact
+        const std::vector<int32_t> subset(keep.begin(), keep.end());                // ascending by construction
+        ge_nn_cfg cfg;
+        ge_nn_cfg_default(&cfg);
+        cfg.metric = config.device.neighbors_metric == "dot" ? GE_NN_DOT : GE_NN_COSINE;
+        cfg.device = config.device.id;
+        ge_nn *raw = nullptr;
+        check(ge_nn_create(rows.data(), V, D, subset.data(), (int64_t)subset.size(), &cfg, &raw));
+        struct Del { void operator()(ge_nn *p) const { ge_nn_destroy(p); } };
+        std::unique_ptr<ge_nn, Del> nn(raw);
+        check(ge_nn_query_rows(nn.get(), nullptr, kept, K, 1, index.data(), score.data()));
+    }
+    std::vector<int32_t> position((size_t)V, -1);                                   // vertex id -> line of the dict file
+    for (size_t k = 0; k < keep.size(); ++k) position[(size_t)keep[k]] = (int32_t)k;
+    std::filesystem::create_directories(outputFolder);
+    const std::string file = fileName + ".neighbors.tsv";
+    std::ofstream out(outputFolder + "/" + file);
+    if (!out) throw std::runtime_error("cannot open " + file + " in " + outputFolder);
+    for (auto &l : config.banner()) out << "# " << l << "\n";
+    std::string line;
+    char num[40];
+    for (size_t k = 0; k < keep.size(); ++k) {
+        line = std::to_string(k);
+        for (int j = 0; j < K; ++j) {
+            line += '\t'; line += std::to_string(position[(size_t)index[k * (size_t)K + (size_t)j]]);
+            line += '\t'; line.append(num, (size_t)java_format_11_6E_to((double)score[k * (size_t)K + (size_t)j], num));
+        }
+        line += '\n';
+        out.write(line.data(), (std::streamsize)line.size());
+    }
+    return "wrote " + std::to_string(K) + " " + config.device.neighbors_metric + " neighbours of " + std::to_string(kept) + " vertices to " + outputFolder + "/" + file;
+}
+
 // ------------------------------------------------------------------------------------------------
 // EmbeddingTextWriter (J/util/write/EmbeddingTextWriter.java)
 // ------------------------------------------------------------------------------------------------
 class EmbeddingTextWriter {
 public:
     EmbeddingTextWriter(const std::string &fileName, const Configuration &config)
-        : vectors_(fileName + ".vectors.tsv"), dict_(fileName + ".dict.tsv"), config_(config) {
-        write_[URI] = config.output.has_uri; write_[BLANK] = config.output.has_blank; write_[LITERAL] = config.output.has_literal;
-    }
+        : vectors_(fileName + ".vectors.tsv"), dict_(fileName + ".dict.tsv"), config_(config) {}
     // returns the number of vectors written
     long long write(const Optimum &optimum, const CoOccurrenceMatrix &m, const std::string &outputFolder) {
         std::filesystem::create_directories(outputFolder);      // Files.createDirectories(outputFolder)
@@ -1157,20 +1239,7 @@ public:
         const int D = V > 0 ? (int)(optimum.result.size() / (size_t)V) : config_.dim;     // config.dim, or the k columns `device.pca: apply` left
         static const char *names[3] = {"URI", "BLANK", "LITERAL"};
         long long written = 0;
-        // which vertices are written (type switch, then the prefix filter of that type: EmbeddingTextWriter.java:100-131), in order
-        std::vector<int> keep;
-        for (int i = 0; i < V; ++i) {
-            const int8_t type = m.getType(i);
-            if (!write_[type]) continue;
-            const std::vector<std::string> &pre = type == URI ? config_.output.uri : type == BLANK ? config_.output.blank : config_.output.literal;
-            if (!pre.empty()) {
-                const std::string key = m.getKey(i);
-                bool any = false;
-                for (auto &p : pre) if (key.compare(0, p.size(), p) == 0) { any = true; break; }
-                if (!any) continue;
-            }
-            keep.push_back(i);
-        }
+        const std::vector<int> keep = keptVertices(config_, m);
         // the text of the vectors file is 13 bytes per value (60 M values for 300 k vertices at dim 200): blocks of rows are
         // formatted by all host threads, written in order
         const int T = std::max(1, std::min(config_.getThreads() > 1 ? config_.getThreads() : (int)std::thread::hardware_concurrency(), 32));
@@ -1211,7 +1280,6 @@ public:
 private:
     std::string vectors_, dict_;
     const Configuration &config_;
-    bool write_[3];
 };
 
 }  // namespace ge_host

@@ -1,5 +1,6 @@
 // geglove -c <config.yml> : the reference's CLI (J/Main.java:133-160) over the MI355X library.
-// Same single flag, same settings banner, same output files ./out/<name>.{vectors,dict}.tsv.
+// Same single flag, same settings banner, same output files ./out/<name>.{vectors,dict}.tsv
+// (and <name>.neighbors.tsv with `device: { neighbors: K }`).
 #include <ctime>
 #include "ge_host.hpp"
 
@@ -10,6 +11,13 @@ static void log_info(const std::string &who, const std::string &msg) {      // l
     const std::time_t t = std::time(nullptr);
     std::strftime(ts, sizeof ts, "%H:%M:%S", std::localtime(&t));
     std::printf("%s %-5s %-25s :: %s\n", ts, "INFO", who.c_str(), msg.c_str());
+    std::fflush(stdout);
+}
+static void log_warn(const std::string &who, const std::string &msg) {
+    char ts[16];
+    const std::time_t t = std::time(nullptr);
+    std::strftime(ts, sizeof ts, "%H:%M:%S", std::localtime(&t));
+    std::printf("%s %-5s %-25s :: %s\n", ts, "WARN", who.c_str(), msg.c_str());
     std::fflush(stdout);
 }
 static void log_error(const std::string &msg) {
@@ -72,6 +80,12 @@ static void runProgram(const Configuration &config) {                       // J
     EmbeddingTextWriter writer(outFileName, config);
     const long long n = writer.write(optimum, bca, "out");
     log_info("EmbeddingTextWriter", "wrote " + std::to_string(n) + " vectors to out/" + writer.vectorsFile());
+    if (config.writingNeighbors()) {
+        std::string warning;
+        const std::string done = writeNeighbors(config, optimum, bca, outFileName, "out", warning);
+        if (!warning.empty()) log_warn("Neighbors", warning);
+        log_info("Neighbors", done);
+    }
 }
 
 int main(int argc, char **argv) {

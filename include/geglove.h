@@ -533,6 +533,53 @@ ge_status ge_glove_pca_transform(const ge_pca *p, ge_glove *h, float *out);     
 ge_status ge_pca_last_kernel_ms(const ge_pca *p, float *fit_ms, float *transform_ms);
 void      ge_pca_destroy(ge_pca *p);
 
+/* ------------------------------------------------------------------------------------------
+ * Top-k nearest neighbours over a table of vectors: which rows lie closest to this one?  Exact (every candidate is scored),
+ * on one device.  The reference stops at the vectors file and has no counterpart, so these are product semantics:
+ *   prepared row  COSINE: n = sqrt(sum_d x_d^2), accumulated in fp64 in ascending d; xh_d = (float)((double)x_d / n), rounded
+ *                 once; a zero row stays zero.  DOT: xh = x.  Query vectors given as values are prepared the same way.
+ *   score         s(q, c) = sum_d xh_q[d] * xh_c[d], an fp32 fmaf chain from 0 in ascending d (k_nn_score_select on the fp32
+ *                 matrix cores, which give exactly that chain).  A score depends on its two rows only: not on the tile, the
+ *                 batch or the other candidates.  A sum that overflows to NaN ranks, and is reported, as -inf.
+ *   result        per query the first k candidates in a total order: score descending as fp32 compares them (so -0 = +0), equal
+ *                 scores by ascending row id.  With exclude_self the query's own row id is not a candidate.  out_index holds
+ *                 ORIGINAL row ids.  Scores are deterministic and the order is total, so the bytes of a result are a function
+ *                 of the input alone: no float atomics, no order-dependent selection.
+ * Limits, checked before any device work (GE_ERR_ARG without a GPU): 1 <= dim <= 1024; 1 <= k <= 128;
+ * k <= candidates - (exclude_self ? 1 : 0); 1 <= n_rows < 2^31 - 1 and n_rows * dim <= 2^35 floats (what one device allocation
+ * of the index may hold); the subset strictly ascending and in range; query ids that are members of the index; a known metric.
+ * Non-finite input rows or query vectors: GE_ERR_ARG ("non-finite input").  No device: GE_ERR_HIP.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct ge_nn ge_nn;
+enum { GE_NN_COSINE = 0, GE_NN_DOT = 1 };
+typedef struct {
+    int32_t metric;          /* GE_NN_COSINE or GE_NN_DOT */
+    int32_t device;          /* HIP device ordinal */
+    void   *stream;          /* hipStream_t or NULL */
+} ge_nn_cfg;
+void      ge_nn_cfg_default(ge_nn_cfg *cfg);              /* cosine, device 0, null stream */
+int32_t   ge_nn_cfg_size(void);
+/* rows: HOST float[n_rows * dim], row-major; uploaded in slabs.  subset: NULL (all rows are candidates; n_subset is ignored)
+ * or n_subset strictly ascending row ids = the candidates.  The index lives on the device until ge_nn_destroy. */
+ge_status ge_nn_create(const float *rows, int64_t n_rows, int32_t dim, const int32_t *subset, int64_t n_subset,
+                       const ge_nn_cfg *cfg, ge_nn **out);
+/* The same on the vectors a trainer handle holds -- (focus + context) / 2, what ge_glove_extract_f32 returns -- without the
+ * trip through host memory; bit for bit the index, and hence the results, ge_nn_create builds from that output.  Runs on the
+ * handle's device and writes no trainer table. */
+ge_status ge_glove_nn_create(ge_glove *h, const int32_t *subset, int64_t n_subset, const ge_nn_cfg *cfg, ge_nn **out);
+/* query_ids: NULL (every indexed row, in order; n_queries must then be the number of indexed rows) or n_queries row ids that
+ * are members of the index.  out_index, out_score: HOST [n_queries * k] each. */
+ge_status ge_nn_query_rows(ge_nn *p, const int32_t *query_ids, int64_t n_queries, int32_t k, int32_t exclude_self,
+                           int32_t *out_index, float *out_score);
+/* vectors: HOST float[n_queries * dim] */
+ge_status ge_nn_query_vectors(ge_nn *p, const float *vectors, int64_t n_queries, int32_t k,
+                              int32_t *out_index, float *out_score);
+ge_status ge_nn_get(const ge_nn *p, int64_t *n_indexed, int32_t *dim, int32_t *metric);   /* any out pointer may be NULL */
+/* Device time of building the index and of the handle's last query call (its kernels, query preparation included), hipEvents
+ * around the kernels, in milliseconds (0 = none ran); copies are not counted.  Either out pointer may be NULL. */
+ge_status ge_nn_last_kernel_ms(const ge_nn *p, float *prepare_ms, float *query_ms);
+void      ge_nn_destroy(ge_nn *p);
+
 /* ------------------------------------------------------------------------------------------ */
 const char *ge_last_error(void);     /* message of the calling thread's last failed call */
 const char *ge_version(void);

@@ -741,7 +741,7 @@ __global__ __launch_bounds__(256, (NCH == 1 && VW == 4 && OPT == GE_OPT_ADAGRAD)
         int run_len = 0;
         // the staged nonzeros have arrived before the walk starts: inside it only row traffic is pending
         asm volatile("" : "+v"(oth[0]), "+v"(oth[1]), "+v"(ww[0]), "+v"(ww[1]), "+v"(ll[0]), "+v"(ll[1]));
-        bool again = false;
+        bool again = false, recut = false;
         // One nonzero.  CUR (0 / 1) names the set that holds its streamed rows; the other set is requested for the next one first
         // thing, before this step waits for anything.
         auto step = [&](const int pos, auto CUR) {
@@ -752,6 +752,8 @@ __global__ __launch_bounds__(256, (NCH == 1 && VW == 4 && OPT == GE_OPT_ADAGRAD)
             // them (same wave, same address: in order) and wait right here, so that on the common path the set is known to be
             // older than those stores and the wait for it leaves them in flight.
             if (again) { request_streamed(CUR, true); settle(); again = false; }
+            // the previous step cut its run and this one continues on the same resident row: requested here, behind that publish
+            if (recut) { request_resident(); recut = false; }
             if (open_new) {                       // the scalars of a new run; its rows follow below
                 cur_id = skey < 0 ? ~skey : skey;
                 // shared = other workers may hold this row too: hub columns (context side), pieces of a long focus row
@@ -786,7 +788,11 @@ __global__ __launch_bounds__(256, (NCH == 1 && VW == 4 && OPT == GE_OPT_ADAGRAD)
                         }
                 }
             }
-            if (next_new) request_resident();     // after the copies above: it refills aN
+            // A cut keeps the resident row: the next run must start from what memory holds once THIS run is published (its own
+            // delta or stores included -- with one worker the walk stays a sequential program for any flush limit), so the row
+            // is requested behind close_run(), first thing in the next step, instead (same wave, same address: in order).
+            recut = next_new && n_key == skey;
+            if (next_new && !recut) request_resident();     // after the copies above: it refills aN
             // this nonzero's streamed rows
             VT bl[NCH], gbl[NCH], hbl[NCH];
             float bb = 0.0f, gbb = 0.0f, hbb = 0.0f;

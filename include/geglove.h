@@ -126,14 +126,16 @@ typedef struct {
     int32_t hot_columns;    /* GE_HOT_* (HOGWILD mode only)                                            */
     int32_t workers;        /* HOGWILD: number of sequential workers (wavefronts); 0 = fill the device.
                                Workers pull chunks of 128 consecutive nonzeros of the epoch order from a queue
-                               and walk each chunk in stable column order; workers = 1 is fully sequential.
+                               and walk each chunk in stable column order; workers = 1 is fully sequential, for any
+                               flush limit: a cut hub run continues from what it has just published
+                               (tests/test_designed_matrices_gpu.py replays it with flush_every 1, 3, 4, 64).
                                workers = -k fills the device except for k wavefront slots, which stay free for
                                kernels running beside the epoch (the all-reduce of an overlapped exchange). */
     int32_t emb_dtype;      /* GE_DTYPE_*: storage of the focus/context rows                           */
     /* HOGWILD tuning; 0 = the library default everywhere.  These change results (which columns publish by delta,
      * how stale a hub run may get), so they live here and under the YAML `device:` block, not in the environment. */
     float   hot_theta;      /* GE_HOT_AUTO: column j is a hub when count(j) * workers >= hot_theta * N.  Default 0.25 */
-    float   stale_budget;   /* a hub run is cut (delta published, row re-read) every m_j updates with
+    float   stale_budget;   /* a hub run is cut (delta published, row re-read behind the publish) every m_j updates with
                                K_j * m_j <= stale_budget, K_j = expected workers inside column j.  Default 2000
                                (measured: 10 000 is stable at the bench scale, 39 000 diverges)                */
     int32_t flush_every;    /* > 0: cut every hub run after this many updates instead (<= 128)              */

@@ -23,6 +23,7 @@
 // runs once per graph, against minutes for the JVM.  Measured in DESIGN.md.
 
 #include "ge_common.h"
+#include "ge_coo.h"
 #include "ge_jhashmap_dev.h"
 
 #include <algorithm>
@@ -842,38 +843,6 @@ struct PhaseClock {
     }
 };
 
-struct ge_coo {
-    int64_t nnz = 0;
-    int32_t V = 0;
-    struct Free { void operator()(void *q) const { std::free(q); } };
-    std::unique_ptr<int32_t[], Free> I, J;      // nnz entries each; left uninitialised until the device copy fills them
-    std::unique_ptr<float[], Free> X;           //   (a value-initialising container would touch 12 bytes per entry once more)
-    int64_t capacity = 0;                       // entries each array has room for (>= nnz)
-    // Fresh host memory costs more than the copy into it: 520 MB of J and X arrive in 9 ms once their pages exist and in 35 - 60 ms when
-    // every page is met for the first time (tools/r03/pinned_probe.py).  The arrays are therefore allocated BEFORE the main launch, from
-    // the sample's estimate of the total, and their pages are touched by host threads while the device works.
-    bool reserve(int64_t entries) {
-        const size_t bytes = ((size_t)std::max<int64_t>(entries, 1) * 4 + 4095) / 4096 * 4096;
-        void *q[3] = {nullptr, nullptr, nullptr};
-        for (int k = 0; k < 3; ++k)
-            if (posix_memalign(&q[k], (size_t)1 << 21, bytes) != 0) { for (int j = 0; j < k; ++j) std::free(q[j]); return false; }
-        for (int k = 0; k < 3; ++k) (void)madvise(q[k], bytes, MADV_HUGEPAGE);      // where the system allows it: 2 MB pages, 512 times fewer faults
-        I.reset(static_cast<int32_t *>(q[0])); J.reset(static_cast<int32_t *>(q[1])); X.reset(static_cast<float *>(q[2]));
-        capacity = (int64_t)(bytes / 4);
-        return true;
-    }
-    // one write per 4 KB page of the first `entries` entries of the three arrays, slice t of n
-    void touch(int64_t entries, int t, int n) {
-        const int64_t pages = (std::min(entries, capacity) * 4 + 4095) / 4096;
-        for (int a = 0; a < 3; ++a) {
-            volatile char *base = a == 0 ? reinterpret_cast<char *>(I.get()) : a == 1 ? reinterpret_cast<char *>(J.get()) : reinterpret_cast<char *>(X.get());
-            for (int64_t pg = pages * t / n, p1 = pages * (t + 1) / n; pg < p1; ++pg) base[pg * 4096] = 0;
-        }
-    }
-    std::vector<int64_t> row_ptr;
-    double max = 0;
-};
-
 namespace {
 
 template <typename T>
@@ -1201,6 +1170,7 @@ static ge_status ge_bca_build_impl(const ge_csr *out_nbrs, const ge_csr *in_nbrs
 ge_status ge_coo_get(const ge_coo *c, int64_t *nnz, const int32_t **I, const int32_t **J, const float **X,
                      const int64_t **row_ptr, double *max) {
     if (!c) return ge::fail(GE_ERR_ARG, "null ge_coo handle");
+    if (c->device >= 0 && (I || J || X || row_ptr)) GE_CHECK(const_cast<ge_coo *>(c)->to_host());   // a device-resident result comes down once
     if (nnz) *nnz = c->nnz;
     if (I) *I = c->I.get();
     if (J) *J = c->J.get();

@@ -32,6 +32,7 @@ struct LayoutRequest {
     int32_t shared_rows;     // 1: pieces of long focus rows publish by delta (default); 0: plain stores (ablation / tests)
     int32_t pack_rows;       // 1: rows packed whole into chunks (default); 0: fixed cuts every 128 positions (ablation / tests)
     bool    want_hub_index;  // bf16 rows: dense index of the hub columns
+    bool    device_input;    // I, J, X are device arrays (a device-resident ge_coo): read in place, no upload
 };
 
 struct BlockedLayout {
@@ -55,7 +56,7 @@ struct BlockedLayout {
     void release();                  // frees the device arrays
 };
 
-// I, J, X: host arrays of the caller (N entries).  Validates the index ranges (same messages as the host loop it replaces).
+// I, J, X: host arrays of the caller (N entries), or device arrays on the stream's device (rq.device_input).  Validates the index ranges (same messages as the host loop it replaces).
 ge_status build_blocked_layout(const LayoutRequest &rq, const int32_t *I, const int32_t *J, const float *X,
                                hipStream_t stream, BlockedLayout *out);
 

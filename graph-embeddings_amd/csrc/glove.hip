@@ -14,6 +14,7 @@
 // run (ge_glove_info.schedule_bytes).  No MFMA: sparse gather + length-D dot.
 
 #include "ge_common.h"
+#include "ge_coo.h"
 #include "ge_glove_internal.h"
 #include "ge_javarand.h"
 #include "ge_cost.h"
@@ -1416,7 +1417,8 @@ void plan_workers(ge_glove *h) {
 
 // The order a Hogwild epoch visits the nonzeros in.  Device shuffle: the blocked layout of ge_layout.h, built on the device.
 // General order (Java permutation / matrix order): the resident side is always the context row, hub columns are keyed ~j.
-ge_status plan_epoch_layout(ge_glove *h, const int32_t *I, const int32_t *J, const float *X) {
+// device_input: I, J, X are the device arrays of a ge_coo (blocked layout only; ge_glove_create_coo sees to that).
+ge_status plan_epoch_layout(ge_glove *h, const int32_t *I, const int32_t *J, const float *X, bool device_input) {
     const ge_glove_cfg &cfg = h->cfg;
     const int32_t V = cfg.vocab_size;
     const int64_t N = cfg.nnz;
@@ -1434,6 +1436,7 @@ ge_status plan_epoch_layout(ge_glove *h, const int32_t *I, const int32_t *J, con
         rq.shared_rows = (cfg.layout_flags & GE_LAYOUT_PLAIN_LONG_ROWS) ? 0 : 1;
         rq.pack_rows = (cfg.layout_flags & GE_LAYOUT_FIXED_CUTS) ? 0 : 1;
         rq.want_hub_index = h->emb16;
+        rq.device_input = device_input;
         GE_CHECK(ge::build_blocked_layout(rq, I, J, X, h->stream, &h->lay));
         h->n_chunks = h->lay.n_chunks; h->n_hchunks = h->lay.n_hchunks;
         h->hot_cols = h->lay.hot_cols; h->hot_nnz = h->lay.hot_nnz; h->hot_threshold = h->lay.hot_threshold;
@@ -1530,7 +1533,7 @@ ge_status init_state(ge_glove *h) {
     return GE_OK;
 }
 
-ge_status ge_glove_create_impl(const ge_glove_cfg *cfg, const int32_t *I, const int32_t *J, const float *X, ge_glove **out) {
+ge_status ge_glove_create_impl(const ge_glove_cfg *cfg, const int32_t *I, const int32_t *J, const float *X, bool device_input, ge_glove **out) {
     if (!out) return ge::fail(GE_ERR_ARG, "out is null");
     *out = nullptr;
     int32_t rb = 0, re = 0;
@@ -1558,7 +1561,7 @@ ge_status ge_glove_create_impl(const ge_glove_cfg *cfg, const int32_t *I, const 
     GE_HIP(h->alloc(&h->djob, (size_t)cfg->threads));
     if (h->hogwild()) {
         plan_workers(h.get());
-        GE_CHECK(plan_epoch_layout(h.get(), I, J, X));
+        GE_CHECK(plan_epoch_layout(h.get(), I, J, X, device_input));
     }
     clk.lap("epoch layout");
     if (!h->blocked) GE_CHECK(upload_nonzeros(h.get(), I, J, X));
@@ -1567,6 +1570,32 @@ ge_status ge_glove_create_impl(const ge_glove_cfg *cfg, const int32_t *I, const 
     clk.lap("init and the rest");
     *out = h.release();
     return GE_OK;
+}
+
+// The trainer on a ge_coo.  The production handle (Hogwild, device shuffle) on a device-resident matrix builds its layout from the
+// device arrays where they are; everything else goes through the host arrays and is ge_glove_create on them.
+ge_status ge_glove_create_coo_impl(const ge_glove_cfg *cfg, const ge_coo *coo, ge_glove **out) {
+    if (!out) return ge::fail(GE_ERR_ARG, "out is null");
+    *out = nullptr;
+    if (!cfg) return ge::fail(GE_ERR_ARG, "cfg is null");
+    if (!coo) return ge::fail(GE_ERR_ARG, "null ge_coo handle");
+    ge_glove_cfg c = *cfg;
+    if (c.vocab_size != coo->V) return ge::fail(GE_ERR_ARG, "vocab_size %d does not match the matrix (%d)", c.vocab_size, coo->V);
+    if (c.nnz != 0 && c.nnz != coo->nnz) return ge::fail(GE_ERR_ARG, "nnz %lld does not match the matrix (%lld); 0 takes it from there", (long long)c.nnz, (long long)coo->nnz);
+    if (c.xmax != 0 && c.xmax != coo->max) return ge::fail(GE_ERR_ARG, "xmax %.17g does not match the matrix (%.17g); 0 takes it from there", c.xmax, coo->max);
+    c.nnz = coo->nnz; c.xmax = coo->max;
+    if (coo->device >= 0) {
+        if (coo->device != c.device) return ge::fail(GE_ERR_ARG, "the matrix lives on device %d, the handle is asked for on device %d", coo->device, c.device);
+        int32_t rb = c.row_begin, re = c.row_end;
+        if (rb == 0 && re == 0) re = c.vocab_size;
+        if (coo->row_begin < rb || coo->row_end > re)
+            return ge::fail(GE_ERR_ARG, "the matrix holds rows [%d,%d), outside owned rows [%d,%d)", coo->row_begin, coo->row_end, rb, re);
+        if (c.mode == GE_MODE_HOGWILD && c.shuffle == GE_SHUFFLE_DEVICE)
+            return ge_glove_create_impl(&c, coo->dI, coo->dJ, coo->dX, true, out);
+    }
+    const int32_t *I = nullptr, *J = nullptr; const float *X = nullptr;
+    GE_CHECK(ge_coo_get(coo, nullptr, &I, &J, &X, nullptr, nullptr));
+    return ge_glove_create_impl(&c, I, J, X, false, out);
 }
 
 // start of a Hogwild epoch on the handle's stream: cost accumulator and ticket counter zeroed, ev0 behind them
@@ -1839,7 +1868,8 @@ void ge_glove_destroy(ge_glove *h) {
 }
 
 // ---- guarded entry points (bodies above allocate on the host) ----
-ge_status ge_glove_create(const ge_glove_cfg *cfg, const int32_t *I, const int32_t *J, const float *X, ge_glove **out) { GE_GUARD(ge_glove_create_impl(cfg, I, J, X, out)); }
+ge_status ge_glove_create(const ge_glove_cfg *cfg, const int32_t *I, const int32_t *J, const float *X, ge_glove **out) { GE_GUARD(ge_glove_create_impl(cfg, I, J, X, false, out)); }
+ge_status ge_glove_create_coo(const ge_glove_cfg *cfg, const ge_coo *coo, ge_glove **out) { GE_GUARD(ge_glove_create_coo_impl(cfg, coo, out)); }
 ge_status ge_glove_epoch(ge_glove *h, int32_t iteration, double *cost_sum) { GE_GUARD(ge_glove_epoch_impl(h, iteration, cost_sum)); }
 ge_status ge_glove_epoch_order(ge_glove *h, int32_t iteration, int32_t *out, int64_t count) { GE_GUARD(ge_glove_epoch_order_impl(h, iteration, out, count)); }
 

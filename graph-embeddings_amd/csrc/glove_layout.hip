@@ -2,7 +2,7 @@
 //
 // Replaces four serial O(N) host passes of round 1 (range check, column count, placement, flush limits).  Pipeline, all on
 // the handle's stream (N = nonzeros, V = vocabulary, rows = focus rows owned):
-//   upload I, J, X -> k_scan_input (range check + column histogram, wave-aggregated atomics)
+//   upload I, J, X (a device-resident ge_coo is read in place instead) -> k_scan_input (range check + column histogram, wave-aggregated atomics)
 //   -> host: hub columns, their dense rank, their flush limits                      O(V)
 //   -> k_sort_keys (key = hub ? rank(j) : n_hub + i, per-row count of the rest)     O(N)
 //   -> rocprim::radix_sort_pairs (stable: column-major hubs, then the rest grouped by row in matrix order)
@@ -131,9 +131,10 @@ ge_status build_blocked_layout(const LayoutRequest &rq, const int32_t *I, const 
     Dev tmp;
     int32_t *dI = nullptr, *dJ = nullptr; float *dX = nullptr;
     int32_t *d_col = nullptr, *d_row = nullptr; unsigned long long *d_bad = nullptr;
-    GE_HIP(tmp.alloc(&dI, (size_t)N)); GE_HIP(tmp.alloc(&dJ, (size_t)N)); GE_HIP(tmp.alloc(&dX, (size_t)N));
+    if (rq.device_input) { dI = const_cast<int32_t *>(I); dJ = const_cast<int32_t *>(J); dX = const_cast<float *>(X); }      // read only, in place
+    else { GE_HIP(tmp.alloc(&dI, (size_t)N)); GE_HIP(tmp.alloc(&dJ, (size_t)N)); GE_HIP(tmp.alloc(&dX, (size_t)N)); }
     GE_HIP(tmp.alloc(&d_col, (size_t)V)); GE_HIP(tmp.alloc(&d_row, (size_t)rows)); GE_HIP(tmp.alloc(&d_bad, 1));
-    if (N > 0) {
+    if (N > 0 && !rq.device_input) {
         GE_HIP(hipMemcpyAsync(dI, I, sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice, stream));
         GE_HIP(hipMemcpyAsync(dJ, J, sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice, stream));
         GE_HIP(hipMemcpyAsync(dX, X, sizeof(float) * (size_t)N, hipMemcpyHostToDevice, stream));
@@ -151,6 +152,13 @@ ge_status build_blocked_layout(const LayoutRequest &rq, const int32_t *I, const 
     clk.lap("upload + column counts");
     if (bad != ~0ull) {
         const int64_t k = (int64_t)bad;
+        if (rq.device_input) {               // the offending entry comes back from the device for the message
+            int32_t bi = 0, bj = 0;
+            GE_HIP(hipMemcpy(&bi, dI + k, sizeof(int32_t), hipMemcpyDeviceToHost));
+            GE_HIP(hipMemcpy(&bj, dJ + k, sizeof(int32_t), hipMemcpyDeviceToHost));
+            if (bi < rb || bi >= rq.row_end) return ge::fail(GE_ERR_ARG, "I[%lld]=%d outside owned rows [%d,%d)", (long long)k, bi, rb, rq.row_end);
+            return ge::fail(GE_ERR_ARG, "J[%lld]=%d outside [0,%d)", (long long)k, bj, V);
+        }
         if (I[k] < rb || I[k] >= rq.row_end) return ge::fail(GE_ERR_ARG, "I[%lld]=%d outside owned rows [%d,%d)", (long long)k, I[k], rb, rq.row_end);
         return ge::fail(GE_ERR_ARG, "J[%lld]=%d outside [0,%d)", (long long)k, J[k], V);
     }

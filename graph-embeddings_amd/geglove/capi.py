@@ -39,6 +39,7 @@ SYMBOLS = (
     "ge_glove_pca_transform", "ge_pca_last_kernel_ms", "ge_pca_destroy",
     "ge_nn_cfg_default", "ge_nn_cfg_size", "ge_nn_create", "ge_glove_nn_create", "ge_nn_query_rows", "ge_nn_query_vectors", "ge_nn_get",
     "ge_nn_last_kernel_ms", "ge_nn_destroy",
+    "ge_synth_cfg_default", "ge_synth_cfg_size", "ge_synth_coo", "ge_coo_device", "ge_coo_synth_stats", "ge_glove_create_coo",
 )
 GE_NN_COSINE, GE_NN_DOT = 0, 1
 NN_METRICS = {"cosine": GE_NN_COSINE, "dot": GE_NN_DOT}
@@ -112,6 +113,11 @@ class PcaCfg(C.Structure):
 
 class NnCfg(C.Structure):
     _fields_ = [("metric", C.c_int32), ("device", C.c_int32), ("stream", C.c_void_p)]
+
+
+class SynthCfg(C.Structure):
+    _fields_ = [("vocab_size", C.c_int32), ("row_begin", C.c_int32), ("row_end", C.c_int32), ("nnz", C.c_int64),
+                ("seed", C.c_uint64), ("device", C.c_int32), ("stream", C.c_void_p)]
 
 
 class GeError(RuntimeError):
@@ -217,6 +223,7 @@ def lib():
                           "%d here): rebuild with `make -C graph-embeddings_amd/csrc`" % (L.ge_glove_cfg_size(), C.sizeof(GloveCfg)))
     _declare_pca(L)
     _declare_nn(L)
+    _declare_synth(L)
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int:      # default restype -> ge_status
@@ -429,6 +436,86 @@ class Neighbors:
             self.close()
         except Exception:
             pass
+
+
+def _declare_synth(L):
+    """The generator section of include/geglove.h."""
+    vp, i32p, f32p = C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float)
+    L.ge_synth_cfg_default.argtypes = [C.POINTER(SynthCfg)]; L.ge_synth_cfg_default.restype = None
+    L.ge_synth_cfg_size.argtypes = []; L.ge_synth_cfg_size.restype = C.c_int32
+    if L.ge_synth_cfg_size() != C.sizeof(SynthCfg):
+        raise ImportError("libgeglove.so was built from another revision of include/geglove.h (ge_synth_cfg is %d bytes there, %d here): "
+                          "rebuild with `make -C graph-embeddings_amd/csrc`" % (L.ge_synth_cfg_size(), C.sizeof(SynthCfg)))
+    L.ge_synth_coo.argtypes = [C.POINTER(SynthCfg), C.POINTER(vp)]
+    L.ge_coo_device.argtypes = [vp, i32p, C.POINTER(i32p), C.POINTER(i32p), C.POINTER(f32p)]
+    L.ge_coo_synth_stats.argtypes = [vp, C.POINTER(C.c_int64), f32p, C.POINTER(C.c_int64)]
+    L.ge_glove_create_coo.argtypes = [C.POINTER(GloveCfg), vp, C.POINTER(vp)]
+
+
+class Coo:
+    """A ge_coo handle (here: the device-resident result of synth_coo)."""
+
+    def __init__(self, handle, vocab_size):
+        self._h = handle
+        self.vocab_size = vocab_size
+
+    @property
+    def handle(self):
+        return self._h
+
+    def get(self):
+        """(I, J, X, row_ptr, max): numpy copies of the host views (a device-resident result comes down on the first call)."""
+        import numpy as np
+        i32p, f32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_int64)
+        n, mx = C.c_int64(), C.c_double()
+        pI, pJ, pX, pR = i32p(), i32p(), f32p(), i64p()
+        check(lib().ge_coo_get(self._h, C.byref(n), C.byref(pI), C.byref(pJ), C.byref(pX), C.byref(pR), C.byref(mx)))
+        arr = lambda p, m, dt: np.ctypeslib.as_array(p, shape=(m,)).copy() if m else np.zeros(0, dt)
+        return (arr(pI, n.value, np.int32), arr(pJ, n.value, np.int32), arr(pX, n.value, np.float32),
+                arr(pR, self.vocab_size + 1, np.int64), mx.value)
+
+    @property
+    def nnz(self):
+        n = C.c_int64()
+        check(lib().ge_coo_get(self._h, C.byref(n), None, None, None, None, None))
+        return n.value
+
+    def device_views(self):
+        """(device, dI, dJ, dX): the device ordinal (-1: host-resident) and the raw device addresses (None then)."""
+        dev = C.c_int32()
+        pI, pJ, pX = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_float)()
+        check(lib().ge_coo_device(self._h, C.byref(dev), C.byref(pI), C.byref(pJ), C.byref(pX)))
+        addr = lambda p: C.cast(p, C.c_void_p).value
+        return dev.value, addr(pI), addr(pJ), addr(pX)
+
+    def stats(self):
+        """(draws, kernel_ms, peak_bytes) of the generator"""
+        draws, ms, peak = C.c_int64(), C.c_float(), C.c_int64()
+        check(lib().ge_coo_synth_stats(self._h, C.byref(draws), C.byref(ms), C.byref(peak)))
+        return draws.value, ms.value, peak.value
+
+    def close(self):
+        if self._h:
+            lib().ge_coo_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def synth_coo(V, nnz, rows=None, seed=0xC0FFEE, device=0):
+    """ge_synth_coo: the synthetic matrix of include/geglove.h's recipe, generated on `device`.  rows = (row_begin, row_end) of a
+    shard, None = all rows.  Returns a Coo."""
+    cfg = SynthCfg(); lib().ge_synth_cfg_default(C.byref(cfg))
+    cfg.vocab_size, cfg.nnz, cfg.seed, cfg.device = V, nnz, seed & 0xFFFFFFFFFFFFFFFF, device
+    if rows is not None:
+        cfg.row_begin, cfg.row_end = rows
+    h = C.c_void_p()
+    check(lib().ge_synth_coo(C.byref(cfg), C.byref(h)))
+    return Coo(h, V)
 
 
 def check(status):

@@ -132,6 +132,29 @@ class CooMatrix:
     def shuffle(self): pass  # owned by the native trainer
 
 
+class DeviceCooMatrix(CooMatrix):
+    """A CoOccurrenceMatrix over a capi.Coo (capi.synth_coo): the trainer is created from the handle itself
+    (ge_glove_create_coo), so a device-resident matrix never passes through host memory.  I / J / X come down on first use."""
+
+    def __init__(self, coo):
+        self.coo = coo
+        self._V = int(coo.vocab_size)
+        self._nnz = coo.nnz
+        self._max = float(np.float32(0.2)) if coo.device_views()[0] >= 0 else coo.get()[4]
+        self._keys = self._types = None
+        self._host = None
+
+    def _arrays(self):
+        if self._host is None:
+            self._host = self.coo.get()
+        return self._host
+
+    I = property(lambda self: self._arrays()[0])
+    J = property(lambda self: self._arrays()[1])
+    X = property(lambda self: self._arrays()[2])
+    def coOccurrenceCount(self): return int(self._nnz)
+
+
 def _csr_struct(V, csr, keep):
     ptr, idx, w = csr
     ptr = np.ascontiguousarray(ptr, np.int64); idx = np.ascontiguousarray(idx, np.int32)
@@ -230,7 +253,7 @@ class Adagrad:
     J/opt/Optimizer.java, J/opt/IOptimizer.java:6-11) over ge_glove_*.
 
     Extra keyword arguments override config.device.* : mode, shuffle, seed, device, stream,
-    row_range (multi-GPU sharding), learning_rate.
+    row_range (multi-GPU sharding), learning_rate.  coMatrix may be a DeviceCooMatrix (a ge_coo handle).
     """
 
     def __init__(self, coMatrix, config, costFunction, **kw):
@@ -269,6 +292,10 @@ class Adagrad:
         self._rows = (re - rb) if (rb, re) != (0, 0) else self.vocabSize
         self._cfg = cfg
         self._h = C.c_void_p()
+        coo = getattr(coMatrix, "coo", None)
+        if coo is not None:                  # a ge_coo handle: a device-resident one is read in place
+            capi.check(capi.lib().ge_glove_create_coo(C.byref(cfg), coo.handle, C.byref(self._h)))
+            return
         I, J, X = coMatrix.I, coMatrix.J, coMatrix.X
         capi.check(capi.lib().ge_glove_create(C.byref(cfg), _p(I, C.c_int32), _p(J, C.c_int32), _p(X, C.c_float),
                                               C.byref(self._h)))

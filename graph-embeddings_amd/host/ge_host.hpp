@@ -737,6 +737,8 @@ struct CoOccurrenceMatrix {                     // J/util/CoOccurrenceMatrix.jav
     virtual const int32_t *dataI() const = 0;
     virtual const int32_t *dataJ() const = 0;
     virtual const float *dataX() const = 0;
+    // a matrix that IS a library handle (SyntheticCooMatrix): the trainer is created from it (ge_glove_create_coo)
+    virtual const ge_coo *handle() const { return nullptr; }
 };
 
 class BookmarkColoring : public CoOccurrenceMatrix {        // J/bca/BookmarkColoring.java
@@ -774,6 +776,43 @@ private:
     const InMemoryGraph &graph_;
     std::unique_ptr<ge_coo, Del> coo_;
     int64_t nnz_ = 0; const int32_t *I_ = nullptr, *J_ = nullptr; const float *X_ = nullptr; double max_ = 0;
+};
+
+// The synthetic matrix of ge_synth_coo (include/geglove.h has the recipe): generated on the device and left there; the trainer reads
+// it in place through handle().  The host views come down only when somebody asks for them.
+class SyntheticCooMatrix : public CoOccurrenceMatrix {
+public:
+    SyntheticCooMatrix(int32_t vocab_size, int64_t nnz, int32_t row_begin = 0, int32_t row_end = 0, uint64_t seed = 0xC0FFEEull, int device = 0) : V_(vocab_size) {
+        if (ge_synth_cfg_size() != (int32_t)sizeof(ge_synth_cfg))
+            throw std::runtime_error("libgeglove.so and this host were built from different revisions of include/geglove.h; rebuild both");
+        ge_synth_cfg cfg;
+        ge_synth_cfg_default(&cfg);
+        cfg.vocab_size = vocab_size; cfg.nnz = nnz; cfg.row_begin = row_begin; cfg.row_end = row_end; cfg.seed = seed; cfg.device = device;
+        ge_coo *h = nullptr;
+        check(ge_synth_coo(&cfg, &h));
+        coo_.reset(h);
+        check(ge_coo_get(h, &nnz_, nullptr, nullptr, nullptr, nullptr, &max_));
+    }
+    int vocabSize() const override { return V_; }
+    double max() const override { return max_; }
+    std::string getKey(int index) const override { return std::to_string(index); }
+    int8_t getType(int) const override { return 0; }
+    int cIdx_I(int i) const override { return dataI()[i]; }
+    int cIdx_J(int j) const override { return dataJ()[j]; }
+    float cIdx_C(int i) const override { return dataX()[i]; }
+    int coOccurrenceCount() const override { return (int)nnz_; }
+    void shuffle() override {}
+    const int32_t *dataI() const override { fetch(); return I_; }
+    const int32_t *dataJ() const override { fetch(); return J_; }
+    const float *dataX() const override { fetch(); return X_; }
+    const ge_coo *handle() const override { return coo_.get(); }
+    void stats(int64_t *draws, float *kernel_ms, int64_t *peak_bytes) const { check(ge_coo_synth_stats(coo_.get(), draws, kernel_ms, peak_bytes)); }
+private:
+    void fetch() const { if (!I_) check(ge_coo_get(coo_.get(), nullptr, &I_, &J_, &X_, nullptr, nullptr)); }
+    struct Del { void operator()(ge_coo *c) const { ge_coo_destroy(c); } };
+    std::unique_ptr<ge_coo, Del> coo_;
+    int32_t V_ = 0; int64_t nnz_ = 0; double max_ = 0;
+    mutable const int32_t *I_ = nullptr, *J_ = nullptr; mutable const float *X_ = nullptr;
 };
 
 // COO checkpoint (the reference has no on-disk form of the matrix, the format is ours):
@@ -931,7 +970,8 @@ public:
         cfg.flush_every = config.device.flush_every; cfg.blocks_per_cu = config.device.blocks_per_cu;
         cfg.layout_flags = config.device.layout_flags;
         ge_glove *h = nullptr;
-        check(ge_glove_create(&cfg, m.dataI(), m.dataJ(), m.dataX(), &h));
+        if (m.handle()) check(ge_glove_create_coo(&cfg, m.handle(), &h));
+        else check(ge_glove_create(&cfg, m.dataI(), m.dataJ(), m.dataX(), &h));
         h_.reset(h);
     }
     std::string getName() const override { return name_; }

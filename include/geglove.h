@@ -285,6 +285,56 @@ ge_status ge_coo_get(const ge_coo *c, int64_t *nnz, const int32_t **I, const int
                      const float **X, const int64_t **row_ptr, double *max);
 void ge_coo_destroy(ge_coo *c);
 
+/* ------------------------------------------------------------------------------------------
+ * Synthetic co-occurrence matrix, generated on the device ("generated per-shard on device, seed 0xC0FFEE +
+ * gpu"), and a trainer that reads it in place.  The reference has no generator, so these are product semantics.  The recipe is
+ * integer and bit operations only: tests/synth_ref.py is the same recipe in numpy and holds the device output to the last bit.
+ * (geglove/synth.py's host recipe goes through fp64 pow and stays what bench.py uses.)
+ *   notation  SM(s, n) = the (n+1)-th SplitMix64 output of seed s;  hi(u) = u >> 32;  lo(u) = u & 0xFFFFFFFF.
+ *   relabel   the stable argsort of SM(seed ^ 0x77777777, 0 .. V-1): a function of the seed alone, so every shard of one
+ *             matrix sees the same hub columns.
+ *   stream    s = (seed + 0x1000003 * (row_begin + 1)) mod 2^64;  rows = row_end - row_begin.
+ *   draw t    a = SM(s, t), b = SM(s ^ 0x5A5A5A5A, t), c = SM(s ^ 0x0F0F0F0F, t)   for t = 0, 1, ...
+ *     row     i = row_begin + ((hi(a) * rows) >> 32)
+ *     rank    B = bit_length(V);  k = (hi(b) * B) >> 32;  r = 2^k - 1 + (lo(b) >> (32 - k)), r = 0 for k = 0: octave k has
+ *             mass 1 / B over 2^k ranks, a density proportional to 1 / rank.
+ *     void    when r >= V or relabel[r] == i; else j = relabel[r].
+ *     value   e = 3 + ((hi(c) * 10) >> 32);  x = the fp32 with bits ((127 - e) << 23) | (c & 0x7FFFFF), then min(x, 0.2f):
+ *             0 < x <= 0.2, pGloVe-valid.
+ *   result    the diagonal (i, i, 0.2f) of the owned rows plus the first M = nnz - rows distinct valid keys (i, j) in ascending
+ *             t, each with the x of its first occurrence; sorted by (i, j); exactly nnz entries.  A function of the arguments
+ *             alone: not of the ranges the draws were taken in, nor of the machine.  No floating-point atomics.
+ *   budget    8 * M + 1024 draws; a request that does not reach M distinct keys within it is GE_ERR_ARG ("too dense").
+ * Limits, checked before any device work (GE_ERR_ARG without a GPU): V >= 1; 0 <= row_begin < row_end <= V (0,0 = all rows);
+ * rows <= nnz < 2^31; nnz - rows <= rows * (V - 1).  No device: GE_ERR_HIP.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t  vocab_size;          /* V of the whole matrix */
+    int32_t  row_begin, row_end;  /* this shard's rows; 0,0 = all */
+    int64_t  nnz;                 /* EXACT size of the result, diagonal included */
+    uint64_t seed;
+    int32_t  device;              /* HIP device ordinal */
+    void    *stream;              /* hipStream_t or NULL */
+} ge_synth_cfg;
+void      ge_synth_cfg_default(ge_synth_cfg *cfg);        /* seed 0xC0FFEE, device 0, everything else 0 */
+int32_t   ge_synth_cfg_size(void);
+/* The result lives on the device (ge_coo_device); the call returns with the stream drained.  ge_coo_get works on it: its first
+ * call for an array copies I, J, X down once and fills row_ptr; *max = (double)0.2f. */
+ge_status ge_synth_coo(const ge_synth_cfg *cfg, ge_coo **out);
+/* Device views of a result, valid until ge_coo_destroy; all NULL and *device = -1 for a host-resident one (what ge_bca_build
+ * returns).  Any out pointer may be NULL. */
+ge_status ge_coo_device(const ge_coo *c, int32_t *device, const int32_t **dI, const int32_t **dJ, const float **dX);
+/* What the generator did: *draws = t* + 1, the draws up to the one that delivered the last key (a function of the arguments);
+ * *kernel_ms = device time of its kernels, sorts and scans (hipEvents); *peak_bytes = the most device memory it held at once,
+ * the result included.  GE_ERR_STATE for a ge_coo that was not generated.  Any out pointer may be NULL. */
+ge_status ge_coo_synth_stats(const ge_coo *c, int64_t *draws, float *kernel_ms, int64_t *peak_bytes);
+/* ge_glove_create on a ge_coo.  cfg->nnz and cfg->xmax are taken from the matrix (each must be 0 or equal to its value),
+ * vocab_size must match, the rows must lie inside cfg's row_begin / row_end, a device-resident ge_coo must live on cfg->device.
+ * GE_MODE_HOGWILD + GE_SHUFFLE_DEVICE on a device-resident ge_coo: the layout is built from the device arrays in place, no host
+ * copy and no upload.  Every other case reads the host arrays (ge_coo_get) and equals ge_glove_create on them.  The handle
+ * keeps nothing of the ge_coo: it may be destroyed right after the call. */
+ge_status ge_glove_create_coo(const ge_glove_cfg *cfg, const ge_coo *coo, ge_glove **out);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Literal-similarity edges.  Replaces the compare loop of Rdf2GrphConverter.convert
  * (J/convert/Rdf2GrphConverter.java:127-186): for one CompareGroup, CompareJob i (J/compare/CompareJob.java:33-51)

@@ -18,6 +18,8 @@
 #include "ge_glove_internal.h"
 #include "ge_javarand.h"
 #include "ge_cost.h"
+#include "ge_exact.h"
+#include "ge_strata.h"
 #include "ge_layout.h"
 
 #include <algorithm>
@@ -88,12 +90,7 @@ __global__ void k_cost_terms(const float *X, int64_t n, int kind, double xmax, d
 // Keyed bijection of [0, 2^b) (odd multiply, xor-shift, add key: each step invertible),
 // cycle-walked into [0, N).  2^b < 2N so the expected number of rounds is < 2.
 __host__ __device__ __forceinline__ uint32_t bij_round(uint32_t x, const GloveParams &p) {
-    const uint32_t m = p.bij_mask, s = p.bij_shift;
-    x = (x + p.bij_key[0]) & m;  x = (x * 0x9E3779B1u) & m;  x ^= x >> s;
-    x = (x + p.bij_key[1]) & m;  x = (x * 0x85EBCA6Bu) & m;  x ^= x >> s;
-    x = (x + p.bij_key[2]) & m;  x = (x * 0xC2B2AE35u) & m;  x ^= x >> s;
-    x = (x + p.bij_key[3]) & m;  x = (x * 0x27D4EB2Fu) & m;  x ^= x >> s;
-    return x;
+    return ge::bij_mix(x, p.bij_mask, p.bij_shift, p.bij_key);
 }
 __device__ __forceinline__ int64_t map_index(const GloveParams &p, int64_t k) {
     if (p.order_mode == ORDER_PERM) return p.perm[k];
@@ -219,78 +216,10 @@ __global__ __launch_bounds__(64) void k_adagrad_exact(GloveParams p, int64_t k_b
                                                       float *job_cost) {
     extern __shared__ float s_prod[];
     const int lane = threadIdx.x;
-    const int32_t D = p.D;
-    const double lr = (double)p.lr;
     float cost = 0.0f;
     for (int64_t k = k_begin; k < k_end; ++k) {
         const int64_t idx = map_index(p, k);
-        const int32_t bu = p.I[idx], bv = p.J[idx];
-        const float x = p.X[idx];
-        float *foc = p.focus + (int64_t)bu * D, *ctx = p.context + (int64_t)bv * D;
-        float *g1s = p.gsf + (int64_t)bu * D,   *g2s = p.gsc + (int64_t)bv * D;
-        for (int32_t d = lane; d < D; d += 64) s_prod[d] = foc[d] * ctx[d];
-        __syncthreads();
-        float ic = 0.0f;
-        for (int32_t d = 0; d < D; ++d) ic = ic + s_prod[d];
-        double l; float w;
-        cost_terms<true>(p.cost_kind, x, p.xmax, l, w);
-        ic = (float)((double)ic + ((double)(p.fbias[bu] + p.cbias[bv]) - l));
-        float wc = w * ic;
-        cost = (float)((double)cost + (0.5 * (double)wc) * (double)ic);
-        __syncthreads();
-        if (p.opt == GE_OPT_ADAGRAD) {
-            for (int32_t d = lane; d < D; d += 64) {
-                const float f = foc[d], c = ctx[d];
-                const float grad1 = wc * c;
-                const float grad2 = wc * f;
-                foc[d] = (float)((double)f - ((double)grad1 / sqrt((double)g1s[d])) * lr);
-                ctx[d] = (float)((double)c - ((double)grad2 / sqrt((double)g2s[d])) * lr);
-                g1s[d] = g1s[d] + grad1 * grad1;
-                g2s[d] = g2s[d] + grad2 * grad2;
-            }
-            if (lane == 0) {
-                p.fbias[bu] = (float)((double)p.fbias[bu] - (double)wc / sqrt((double)p.gsfb[bu]));
-                p.cbias[bv] = (float)((double)p.cbias[bv] - (double)wc / sqrt((double)p.gscb[bv]));
-                wc = wc * wc;
-                p.gsfb[bu] = p.gsfb[bu] + wc;
-                p.gscb[bv] = p.gscb[bv] + wc;
-            }
-        } else {
-            // Adam.java:103-145 / AMSGrad.java:117-160.  All moment arithmetic is fp32 (beta1, 1-beta1, ... are floats),
-            // the parameter step goes through fp64 exactly as `focus[d1] -= correction * m1 / (sqrt(v1) + epsilon)`.
-            const bool ams = p.opt == GE_OPT_AMSGRAD;
-            const float beta1 = 0.9f, beta2 = 0.999f, epsilon = 1e-7f;
-            const float omb1 = 1 - beta1, omb2 = 1 - beta2;
-            float *m2f = p.m2f + (int64_t)bu * D, *m2c = p.m2c + (int64_t)bv * D;
-            auto fmaxj = [](float a, float b) { return (a <= b) ? b : ((a + b) != (a + b) ? __builtin_nanf("") : a); };   // FastMath.max
-            auto step = [&](float par, float m, float v) -> float {
-                return ams ? (float)((double)par - lr / (sqrt((double)v) + (double)epsilon) * (double)m)
-                           : (float)((double)par - p.correction * (double)m / (sqrt((double)v) + (double)epsilon));
-            };
-            for (int32_t d = lane; d < D; d += 64) {
-                const float f = foc[d], c = ctx[d];
-                const float grad_u = wc * c, grad_v = wc * f;
-                const float m1 = beta1 * g1s[d] + omb1 * grad_u;
-                const float m2 = beta1 * g2s[d] + omb1 * grad_v;
-                float v1 = beta2 * m2f[d] + omb2 * (grad_u * grad_u);
-                float v2 = beta2 * m2c[d] + omb2 * (grad_v * grad_v);
-                if (ams) { v1 = fmaxj(m2f[d], v1); v2 = fmaxj(m2c[d], v2); }
-                foc[d] = step(f, m1, v1);
-                ctx[d] = step(c, m2, v2);
-                g1s[d] = m1; g2s[d] = m2; m2f[d] = v1; m2c[d] = v2;
-            }
-            if (lane == 0) {
-                const float m1 = beta1 * p.gsfb[bu] + omb1 * wc;
-                const float m2 = beta1 * p.gscb[bv] + omb1 * wc;
-                float v1 = beta2 * p.m2fb[bu] + omb2 * (wc * wc);
-                float v2 = beta2 * p.m2cb[bv] + omb2 * (wc * wc);
-                if (ams) { v1 = fmaxj(p.m2fb[bu], v1); v2 = fmaxj(p.m2cb[bv], v2); }
-                p.fbias[bu] = step(p.fbias[bu], m1, v1);
-                p.cbias[bv] = step(p.cbias[bv], m2, v2);
-                p.gsfb[bu] = m1; p.gscb[bv] = m2; p.m2fb[bu] = v1; p.m2cb[bv] = v2;
-            }
-        }
-        __syncthreads();   // the next nonzero may read what this one wrote (same wave, program order)
+        ge::exact_update(p, p.I[idx], p.J[idx], p.X[idx], s_prod, lane, cost);      // ge_exact.h: shared with k_adagrad_strata
     }
     if (lane == 0) *job_cost = cost;
 }
@@ -1021,8 +950,10 @@ struct ge_glove {
     std::vector<int32_t> host_key;    // general order: sort key per nonzero (what the kernel stages as `key`)
     int32_t hot_cols = 0;
     int64_t hot_nnz = 0, hot_threshold = 0;
+    ge::Strata strata;                // GE_MODE_STRATIFIED: the tile layout (ge_strata.h)
 
     bool hogwild() const { return cfg.mode == GE_MODE_HOGWILD; }
+    bool stratified() const { return cfg.mode == GE_MODE_STRATIFIED; }
     bool moments() const { return cfg.opt != GE_OPT_ADAGRAD; }      // Adam / AMSGrad keep M2* next to M1*
     bool interleaved() const { return hogwild() && (cfg.layout_flags & GE_LAYOUT_SEPARATE_TABLES) == 0; }   // a side is one table of records
     template <typename T> hipError_t alloc(T **out, size_t n) {
@@ -1254,8 +1185,12 @@ ge_status validate_config(const ge_glove_cfg *cfg, const int32_t *I, const int32
     if (cfg->cost != GE_COST_GLOVE && cfg->cost != GE_COST_PGLOVE) return ge::fail(GE_ERR_ARG, "Invalid cost function %d", cfg->cost);
     if (cfg->opt < GE_OPT_ADAGRAD || cfg->opt > GE_OPT_AMSGRAD) return ge::fail(GE_ERR_ARG, "Invalid optimization method %d", cfg->opt);
     if (cfg->threads < 1) return ge::fail(GE_ERR_ARG, "threads must be >= 1");
-    if (cfg->mode != GE_MODE_HOGWILD && cfg->mode != GE_MODE_DETERMINISTIC) return ge::fail(GE_ERR_ARG, "invalid mode %d", cfg->mode);
+    if (cfg->mode != GE_MODE_HOGWILD && cfg->mode != GE_MODE_DETERMINISTIC && cfg->mode != GE_MODE_STRATIFIED) return ge::fail(GE_ERR_ARG, "invalid mode %d", cfg->mode);
+    if (cfg->strata < 0 || cfg->strata > 2048) return ge::fail(GE_ERR_ARG, "strata must lie in [0, 2048] (got %d; 0 = the default for the matrix)", cfg->strata);
+    if (cfg->strata != 0 && cfg->mode != GE_MODE_STRATIFIED) return ge::fail(GE_ERR_ARG, "strata = %d needs mode = GE_MODE_STRATIFIED", cfg->strata);
     if (cfg->shuffle < GE_SHUFFLE_JAVA || cfg->shuffle > GE_SHUFFLE_NONE) return ge::fail(GE_ERR_ARG, "invalid shuffle %d", cfg->shuffle);
+    if (cfg->mode == GE_MODE_STRATIFIED && cfg->shuffle == GE_SHUFFLE_JAVA)
+        return ge::fail(GE_ERR_ARG, "the stratified mode cannot follow a global Fisher-Yates order: shuffle must be device or none");
     if (cfg->workers < -(1 << 20)) return ge::fail(GE_ERR_ARG, "workers out of range");
     if (cfg->emb_dtype != GE_DTYPE_F32 && cfg->emb_dtype != GE_DTYPE_BF16) return ge::fail(GE_ERR_ARG, "invalid emb_dtype %d", cfg->emb_dtype);
     const bool emb16 = cfg->emb_dtype == GE_DTYPE_BF16;
@@ -1564,7 +1499,10 @@ ge_status ge_glove_create_impl(const ge_glove_cfg *cfg, const int32_t *I, const 
         GE_CHECK(plan_epoch_layout(h.get(), I, J, X, device_input));
     }
     clk.lap("epoch layout");
-    if (!h->blocked) GE_CHECK(upload_nonzeros(h.get(), I, J, X));
+    if (h->stratified()) {            // its own copies of the nonzeros, sorted by tile
+        const int32_t P = cfg->strata > 0 ? cfg->strata : ge::strata_default_p(h->rows, cfg->nnz);
+        GE_CHECK(ge::strata_build(&h->strata, P, cfg->vocab_size, cfg->nnz, I, J, X, h->stream));
+    } else if (!h->blocked) GE_CHECK(upload_nonzeros(h.get(), I, J, X));
     if (cfg->shuffle == GE_SHUFFLE_JAVA) GE_CHECK(init_permutation(h.get()));
     GE_CHECK(init_state(h.get()));
     clk.lap("init and the rest");
@@ -1625,6 +1563,16 @@ ge_status ge_glove_epoch_impl(ge_glove *h, int32_t iteration, double *cost_sum) 
     }
     GloveParams p;
     fill_params(h, p, iteration);
+    if (h->stratified()) {
+        ge::ExactParams e{p.focus, p.context, p.fbias, p.cbias, p.gsf, p.gsc, p.gsfb, p.gscb, p.m2f, p.m2c, p.m2fb, p.m2cb,
+                          p.correction, p.xmax, p.opt, p.D, p.cost_kind, p.lr};
+        double total = 0.0;
+        GE_CHECK(ge::strata_epoch(&h->strata, e, h->cfg.seed, iteration, h->cfg.shuffle == GE_SHUFFLE_DEVICE, h->stream, h->ev0, h->ev1,
+                                  &h->last_launches, &total));
+        GE_HIP(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+        if (cost_sum) *cost_sum = total;
+        return GE_OK;
+    }
     const int T = h->cfg.mode == GE_MODE_DETERMINISTIC ? h->cfg.threads : 0;
     if (T > 0) {
         const int64_t per = N / T;
@@ -1658,9 +1606,13 @@ ge_status ge_glove_epoch_impl(ge_glove *h, int32_t iteration, double *cost_sum) 
 
 ge_status ge_glove_epoch_order_impl(ge_glove *h, int32_t iteration, int32_t *out, int64_t count) {
     if (!h || !out) return ge::fail(GE_ERR_ARG, "null argument");
-    if (h->cfg.mode != GE_MODE_HOGWILD) return ge::fail(GE_ERR_STATE, "epoch order is defined for GE_MODE_HOGWILD handles");
+    if (h->cfg.mode == GE_MODE_DETERMINISTIC) return ge::fail(GE_ERR_STATE, "epoch order is defined for GE_MODE_HOGWILD and GE_MODE_STRATIFIED handles");
     const int64_t N = h->cfg.nnz;
     if (count != N) return ge::fail(GE_ERR_ARG, "the epoch visits %lld nonzeros", (long long)N);
+    if (h->stratified()) {
+        ge::strata_order(&h->strata, h->cfg.seed, iteration, h->cfg.shuffle == GE_SHUFFLE_DEVICE, out);
+        return GE_OK;
+    }
     GloveParams p;
     fill_params(h, p, iteration);
     std::vector<int32_t> key, border, cstart;        // blocked layout: copied back from the device (a testing aid, not a hot path)
@@ -1775,6 +1727,7 @@ ge_status ge_glove_get_info(ge_glove *h, ge_glove_info *info) {
     info->hot_columns = h->hot_cols; info->hot_nonzeros = h->hot_nnz; info->hot_threshold = h->hot_threshold;
     info->chunks = h->n_chunks; info->hub_chunks = h->n_hchunks; info->long_rows = h->lay.long_rows; info->shared_chunks = h->lay.shared_chunks;
     info->flush_min = h->flush_every; info->row_stride = h->ds;
+    if (h->stratified()) { info->blocks = info->groups_in_flight = h->strata.P; info->strata = h->strata.P; info->strata_path = h->strata.path; }
     info->placements = h->placements; info->placement_best_ms = h->place_best_ms; info->placement_worst_ms = h->place_worst_ms;
     if (h->blocked) {
         // one row access = the bytes a wavefront's row instruction moves: the row width of the table it touches
@@ -1862,6 +1815,7 @@ void ge_glove_destroy(ge_glove *h) {
     for (hipEvent_t e : h->seg_ev) if (e) (void)hipEventDestroy(e);
     for (void *q : h->owned) (void)hipFree(q);
     h->lay.release();
+    h->strata.release();
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     delete h;

@@ -14,7 +14,7 @@ GE_OK, GE_ERR_ARG, GE_ERR_OOM, GE_ERR_HIP, GE_ERR_STATE, GE_ERR_OVERFLOW = 0, -1
 GE_COST_GLOVE, GE_COST_PGLOVE = 0, 1
 GE_OPT_ADAGRAD, GE_OPT_ADAM, GE_OPT_AMSGRAD = 0, 1, 2
 GE_NORM_NONE, GE_NORM_UNITY, GE_NORM_COUNTS = 0, 1, 2
-GE_MODE_HOGWILD, GE_MODE_DETERMINISTIC = 0, 1
+GE_MODE_HOGWILD, GE_MODE_DETERMINISTIC, GE_MODE_STRATIFIED = 0, 1, 2
 GE_SHUFFLE_JAVA, GE_SHUFFLE_DEVICE, GE_SHUFFLE_NONE = 0, 1, 2
 GE_HOT_AUTO, GE_HOT_NONE, GE_HOT_ALL = 0, 1, 2
 GE_DTYPE_F32, GE_DTYPE_BF16 = 0, 1
@@ -34,7 +34,7 @@ SYMBOLS = (
     "ge_bca_build", "ge_coo_get", "ge_coo_destroy", "ge_exchange_turn_bf16", "ge_glove_context_layout",
     "ge_local_group_create", "ge_local_group_destroy", "ge_local_group_abort", "ge_rccl_unique_id", "ge_rccl_selftest", "ge_sync_cfg_size", "ge_sync_create", "ge_sync_begin", "ge_sync_finish", "ge_sync_turn", "ge_sync_sync",
     "ge_sync_epoch", "ge_sync_hub_rows", "ge_sync_hub_exchange", "ge_sync_hub_exchange_live", "ge_sync_live_rows", "ge_sync_hub_plan", "ge_sync_replicate", "ge_sync_allreduce_f64", "ge_sync_destroy",
-    "ge_sim_cfg_default", "ge_sim_cfg_size", "ge_sim_pattern_supported", "ge_similarity_pairs", "ge_sim_pairs_get", "ge_sim_pairs_destroy", "ge_copy_bandwidth", "ge_last_error", "ge_version", "ge_glove_cfg_size", "ge_bca_cfg_size", "ge_device_count",
+    "ge_sim_cfg_default", "ge_sim_cfg_size", "ge_sim_pattern_supported", "ge_similarity_pairs", "ge_sim_pairs_get", "ge_sim_pairs_destroy", "ge_copy_bandwidth", "ge_last_error", "ge_version", "ge_glove_cfg_size", "ge_glove_info_size", "ge_bca_cfg_size", "ge_device_count",
     "ge_pca_cfg_default", "ge_pca_cfg_size", "ge_pca_fit", "ge_glove_pca_fit", "ge_pca_from_moments", "ge_pca_get", "ge_pca_transform",
     "ge_glove_pca_transform", "ge_pca_last_kernel_ms", "ge_pca_destroy",
     "ge_nn_cfg_default", "ge_nn_cfg_size", "ge_nn_create", "ge_glove_nn_create", "ge_nn_query_rows", "ge_nn_query_vectors", "ge_nn_get",
@@ -53,7 +53,7 @@ class GloveCfg(C.Structure):
                 ("stream", C.c_void_p), ("row_begin", C.c_int32), ("row_end", C.c_int32),
                 ("hot_columns", C.c_int32), ("workers", C.c_int32), ("emb_dtype", C.c_int32),
                 ("hot_theta", C.c_float), ("stale_budget", C.c_float), ("flush_every", C.c_int32),
-                ("blocks_per_cu", C.c_int32), ("layout_flags", C.c_int32)]
+                ("blocks_per_cu", C.c_int32), ("layout_flags", C.c_int32), ("strata", C.c_int32)]
 
 
 class GloveInfo(C.Structure):
@@ -62,7 +62,7 @@ class GloveInfo(C.Structure):
                 ("hot_nonzeros", C.c_int64), ("hot_threshold", C.c_int64), ("chunks", C.c_int64), ("hub_chunks", C.c_int64),
                 ("long_rows", C.c_int64), ("shared_chunks", C.c_int64), ("flush_min", C.c_int32), ("row_stride", C.c_int32),
                 ("runs", C.c_int64), ("schedule_bytes", C.c_int64), ("placements", C.c_int32), ("placement_best_ms", C.c_float),
-                ("placement_worst_ms", C.c_float), ("reserved_", C.c_int32)]
+                ("placement_worst_ms", C.c_float), ("reserved_", C.c_int32), ("strata", C.c_int32), ("strata_path", C.c_int64)]
 
 
 class Csr(C.Structure):
@@ -212,6 +212,7 @@ def lib():
     L.ge_glove_cfg_size.argtypes = []; L.ge_glove_cfg_size.restype = C.c_int32
     L.ge_sim_cfg_size.argtypes = []; L.ge_sim_cfg_size.restype = C.c_int32
     L.ge_bca_cfg_size.argtypes = []; L.ge_bca_cfg_size.restype = C.c_int32
+    L.ge_glove_info_size.argtypes = []; L.ge_glove_info_size.restype = C.c_int32
     if L.ge_bca_cfg_size() != C.sizeof(BcaCfg):
         raise ImportError("libgeglove.so was built from another revision of include/geglove.h (ge_bca_cfg is %d bytes there, %d here): "
                           "rebuild with `make -C graph-embeddings_amd/csrc`" % (L.ge_bca_cfg_size(), C.sizeof(BcaCfg)))
@@ -221,6 +222,9 @@ def lib():
     if L.ge_glove_cfg_size() != C.sizeof(GloveCfg):
         raise ImportError("libgeglove.so was built from another revision of include/geglove.h (ge_glove_cfg is %d bytes there, "
                           "%d here): rebuild with `make -C graph-embeddings_amd/csrc`" % (L.ge_glove_cfg_size(), C.sizeof(GloveCfg)))
+    if L.ge_glove_info_size() != C.sizeof(GloveInfo):
+        raise ImportError("libgeglove.so was built from another revision of include/geglove.h (ge_glove_info is %d bytes there, "
+                          "%d here): rebuild with `make -C graph-embeddings_amd/csrc`" % (L.ge_glove_info_size(), C.sizeof(GloveInfo)))
     _declare_pca(L)
     _declare_nn(L)
     _declare_synth(L)

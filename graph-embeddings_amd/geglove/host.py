@@ -39,7 +39,7 @@ class Configuration:
     Accepts the bean's keys AND the legacy keys present in the shipped YAMLs
     (`bca.reverse`, `bca.predicates`, `similarity[].predicate`), which the Java bean of this
     revision would reject.  New, optional keys live under `device:`:
-      mode: hogwild|deterministic   shuffle: java|device|none   seed: <long>   id: <ordinal>
+      mode: hogwild|deterministic|stratified   strata: <P, 0 = default>   shuffle: java|device|none   seed: <long>   id: <ordinal>
       hot: auto|none|all   workers: <int>   dtype: f32|bf16
       hot_theta, stale_budget, flush_every, blocks_per_cu (ge_glove_cfg; 0 / absent = library default)
       layout: [fixed_cuts, plain_long_rows, separate_tables, packed_records, first_placement]   bca_table_slots, bca_pool_entries (ge_bca_cfg sizing)
@@ -238,7 +238,7 @@ class Optimum:
     def setFinalCost(self, c): self.finalCost = c
 
 
-_MODES = {"hogwild": capi.GE_MODE_HOGWILD, "deterministic": capi.GE_MODE_DETERMINISTIC}
+_MODES = {"hogwild": capi.GE_MODE_HOGWILD, "deterministic": capi.GE_MODE_DETERMINISTIC, "stratified": capi.GE_MODE_STRATIFIED}
 _HOT = {"auto": capi.GE_HOT_AUTO, "none": capi.GE_HOT_NONE, "all": capi.GE_HOT_ALL}
 _SHUFFLES = {"java": capi.GE_SHUFFLE_JAVA, "device": capi.GE_SHUFFLE_DEVICE, "none": capi.GE_SHUFFLE_NONE}
 _LAYOUT = {"default": 0, "fixed_cuts": capi.GE_LAYOUT_FIXED_CUTS, "plain_long_rows": capi.GE_LAYOUT_PLAIN_LONG_ROWS,
@@ -286,6 +286,7 @@ class Adagrad:
         cfg.emb_dtype = {"f32": capi.GE_DTYPE_F32, "bf16": capi.GE_DTYPE_BF16}[str(dev.get("dtype", "f32")).lower()]
         cfg.hot_theta = float(dev.get("hot_theta", 0)); cfg.stale_budget = float(dev.get("stale_budget", 0))
         cfg.flush_every = int(dev.get("flush_every", 0)); cfg.blocks_per_cu = int(dev.get("blocks_per_cu", 0))
+        cfg.strata = int(dev.get("strata", 0))
         lay = dev.get("layout") or []
         for name in ([lay] if isinstance(lay, str) else lay):
             cfg.layout_flags |= _LAYOUT[str(name).lower()]

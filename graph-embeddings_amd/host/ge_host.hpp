@@ -251,6 +251,7 @@ struct Configuration {
     // new, optional block `device:` (never changes the meaning of a reference key)
     struct { std::string mode = "hogwild", shuffle = "device", hot = "auto", dtype = "f32", save_coo, load_coo;
              long long seed = 0; bool has_seed = false; int id = 0; int workers = 0;
+             int strata = 0;        // mode: stratified -- P, 0 = the library's default for the matrix
              // Hogwild tuning (ge_glove_cfg: 0 = library default), layout: list of fixed_cuts | plain_long_rows | separate_tables | packed_records
              double hot_theta = 0, stale_budget = 0; int flush_every = 0, blocks_per_cu = 0, layout_flags = 0;
              long long bca_table_slots = 0, bca_pool_entries = 0;
@@ -345,6 +346,7 @@ struct Configuration {
                     else if (q.first == "seed") { c.device.seed = std::strtoll(q.second.scalar.c_str(), nullptr, 10); c.device.has_seed = true; }
                     else if (q.first == "id") c.device.id = (int)num(&q.second);
                     else if (q.first == "workers") c.device.workers = (int)num(&q.second);
+                    else if (q.first == "strata") c.device.strata = (int)num(&q.second);
                     else if (q.first == "dtype") c.device.dtype = q.second.scalar;
                     else if (q.first == "save_coo") c.device.save_coo = q.second.scalar;      // COO checkpoint
                     else if (q.first == "load_coo") c.device.load_coo = q.second.scalar;
@@ -392,6 +394,10 @@ struct Configuration {
         if (c.device.pca != "off" && c.device.pca != "apply") throw InvalidConfigurationException("Invalid device.pca, choose one of: off, apply");
         if (c.applyingPca() && !c.usingPca()) throw InvalidConfigurationException("device.pca: apply needs a pca block with a variance");
         if (c.applyingPca() && !(c.pca.variance > 0 && c.pca.variance <= 1)) throw InvalidConfigurationException("Invalid PCA parameters, variance must lie in (0, 1]");
+        if (c.device.mode == "stratified" && c.device.shuffle == "java")
+            throw InvalidConfigurationException("device.mode: stratified cannot follow shuffle: java, choose one of: device, none");
+        if (c.device.strata < 0 || c.device.strata > 2048) throw InvalidConfigurationException("Invalid device.strata, choose a number from 1 to 2048 (0 = default)");
+        if (c.device.strata != 0 && c.device.mode != "stratified") throw InvalidConfigurationException("device.strata needs device.mode: stratified");
         if (c.device.neighbors < 0 || c.device.neighbors > 128) throw InvalidConfigurationException("Invalid device.neighbors, choose a number from 1 to 128 (0 = off)");
         if (c.device.neighbors_metric != "cosine" && c.device.neighbors_metric != "dot") throw InvalidConfigurationException("Invalid device.neighbors_metric, choose one of: cosine, dot");
     }
@@ -433,6 +439,7 @@ struct Configuration {
             L.push_back("Using the following similarity metrics:");
             for (auto &s : similarity) L.push_back(similarity_to_string(s));
         } else L.push_back("No similarity matching will be performed");
+        if (device.mode == "stratified") L.push_back("Stratified trainer: " + (device.strata > 0 ? std::to_string(device.strata) + " strata" : std::string("strata chosen from the matrix")));
         if (writingNeighbors()) L.push_back("Nearest neighbours: " + std::to_string(device.neighbors) + " (" + device.neighbors_metric + ")");
         return L;
     }
@@ -940,6 +947,7 @@ struct IOptimizer {                              // J/opt/IOptimizer.java:6-11
     virtual Optimum optimize() = 0;
     virtual std::string getName() const = 0;
     virtual std::vector<double> extractResult() = 0;
+    virtual std::string scheduleNote() const { return std::string(); }      // what the library decided, for the log ("" = nothing to say)
 };
 enum class CostFunction { GLOVE, PGLOVE };       // GloveCost / PGloveCost
 
@@ -960,7 +968,8 @@ public:
         cfg.threads = config.getThreads();
         // Main seeds from the wall clock (Configuration.setThreadLocalRandom(), J/Main.java:62); `device.seed` pins it
         cfg.seed = config.device.has_seed ? config.device.seed : (long long)(std::time(nullptr)) * 1000LL;
-        cfg.mode = config.device.mode == "deterministic" ? GE_MODE_DETERMINISTIC : GE_MODE_HOGWILD;
+        cfg.mode = config.device.mode == "deterministic" ? GE_MODE_DETERMINISTIC : config.device.mode == "stratified" ? GE_MODE_STRATIFIED : GE_MODE_HOGWILD;
+        cfg.strata = config.device.strata;
         cfg.shuffle = config.device.shuffle == "java" ? GE_SHUFFLE_JAVA : config.device.shuffle == "none" ? GE_SHUFFLE_NONE : GE_SHUFFLE_DEVICE;
         cfg.hot_columns = config.device.hot == "none" ? GE_HOT_NONE : config.device.hot == "all" ? GE_HOT_ALL : GE_HOT_AUTO;
         cfg.workers = config.device.workers;
@@ -975,6 +984,13 @@ public:
         h_.reset(h);
     }
     std::string getName() const override { return name_; }
+    std::string scheduleNote() const override {   // stratified handles: P and the epoch's length as a share of the nonzeros
+        ge_glove_info info;
+        if (ge_glove_get_info(h_.get(), &info) != GE_OK || info.strata == 0) return std::string();
+        char b[160];
+        std::snprintf(b, sizeof b, "stratified: P = %d, strata_path / N = %.6g", info.strata, coCount_ > 0 ? (double)info.strata_path / (double)coCount_ : 0.0);
+        return b;
+    }
     Optimum optimize() override {                 // Optimizer.optimize, J/opt/Optimizer.java:66-120
         Optimum opt;
         double finalCost = 0, prevCost = 0;
@@ -1023,7 +1039,7 @@ public:
         : m_(m), config_(config), cf_(cf), progress_(progress) {
         std::string om = config.opt.method; for (auto &ch : om) ch = (char)std::toupper((unsigned char)ch);
         if (om != "ADAGRAD") throw std::invalid_argument("device.gpus > 1 runs opt.method adagrad only (the exchange's merge rule is defined for it)");
-        if (config.device.mode == "deterministic") throw std::invalid_argument("device.gpus > 1 needs device.mode hogwild");
+        if (config.device.mode != "hogwild") throw std::invalid_argument("device.gpus > 1 needs device.mode hogwild");
     }
     std::string getName() const override { return "Adagrad"; }
     std::vector<double> extractResult() override { return result_; }

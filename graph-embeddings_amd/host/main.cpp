@@ -70,6 +70,7 @@ static void runProgram(const Configuration &config) {                       // J
     }
     g_tolerance = config.opt.tolerance;
     std::unique_ptr<IOptimizer> optimizer = createOptimizer(config, bca, progress);
+    if (!optimizer->scheduleNote().empty()) log_info("Optimizer", optimizer->scheduleNote());
     Optimum optimum = optimizer->optimize();
     {
         char b[120];

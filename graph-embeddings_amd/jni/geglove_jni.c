@@ -26,7 +26,7 @@ static void throw_msg(JNIEnv *env, const char *msg) {
 /* Indices of gloveCreate's int options (org.uu.nl.embedding.hip.Native.OPT_*) and float options (TUNE_*): every field of
  * ge_glove_cfg that Main.createOptimizer (J/Main.java:107-131) or the `device:` block can set. */
 enum { OPT_COST, OPT_OPT, OPT_THREADS, OPT_MODE, OPT_SHUFFLE, OPT_DEVICE, OPT_ROW_BEGIN, OPT_ROW_END, OPT_HOT_COLUMNS, OPT_WORKERS,
-       OPT_EMB_DTYPE, OPT_FLUSH_EVERY, OPT_BLOCKS_PER_CU, OPT_LAYOUT_FLAGS, OPT_COUNT };
+       OPT_EMB_DTYPE, OPT_FLUSH_EVERY, OPT_BLOCKS_PER_CU, OPT_LAYOUT_FLAGS, OPT_STRATA, OPT_COUNT };
 enum { TUNE_LEARNING_RATE, TUNE_HOT_THETA, TUNE_STALE_BUDGET, TUNE_COUNT };
 
 /* long gloveCreate(int V, int D, int[] I, int[] J, float[] X, double xmax, long seed, int[] opts, float[] tune)
@@ -53,7 +53,7 @@ JNIEXPORT jlong JNICALL Java_org_uu_nl_embedding_hip_Native_gloveCreate(
     cfg.cost = o[OPT_COST]; cfg.opt = o[OPT_OPT]; cfg.threads = o[OPT_THREADS]; cfg.mode = o[OPT_MODE]; cfg.shuffle = o[OPT_SHUFFLE];
     cfg.device = o[OPT_DEVICE]; cfg.row_begin = o[OPT_ROW_BEGIN]; cfg.row_end = o[OPT_ROW_END]; cfg.hot_columns = o[OPT_HOT_COLUMNS];
     cfg.workers = o[OPT_WORKERS]; cfg.emb_dtype = o[OPT_EMB_DTYPE]; cfg.flush_every = o[OPT_FLUSH_EVERY];
-    cfg.blocks_per_cu = o[OPT_BLOCKS_PER_CU]; cfg.layout_flags = o[OPT_LAYOUT_FLAGS];
+    cfg.blocks_per_cu = o[OPT_BLOCKS_PER_CU]; cfg.layout_flags = o[OPT_LAYOUT_FLAGS]; cfg.strata = o[OPT_STRATA];
     if (t[TUNE_LEARNING_RATE] > 0) cfg.learning_rate = t[TUNE_LEARNING_RATE];
     cfg.hot_theta = t[TUNE_HOT_THETA]; cfg.stale_budget = t[TUNE_STALE_BUDGET];
     jint *pi = (*env)->GetIntArrayElements(env, I, NULL);

@@ -51,8 +51,41 @@ enum { GE_NORM_NONE = 0, GE_NORM_UNITY = 1, GE_NORM_COUNTS = 2 };
  *   :76-77, :88-89).  One wavefront; a parity / reproducibility mode, not a fast one.
  * HOGWILD: the production mode.  Thousands of lane groups update the shared tables without
  *   locks, exactly as the Java worker threads do (J/opt/Optimizer.java:27-28 are plain arrays),
- *   fp32 arithmetic, wave-reduced dot. */
-enum { GE_MODE_HOGWILD = 0, GE_MODE_DETERMINISTIC = 1 };
+ *   fp32 arithmetic, wave-reduced dot.
+ * STRATIFIED: DETERMINISTIC's arithmetic, operation for operation, on P wavefronts at once and still a function of the input
+ *   alone: same bytes run after run, machine after machine, no update lost.  Product semantics (the reference has no counterpart):
+ *   notation   N = nnz, nonzero k = (I[k], J[k], X[k]) in matrix order, P = the number of strata (below).
+ *   partition  r(i) = #{k : I[k] < i},  c(j) = #{k : J[k] < j};  rb(i) = (r(i) * P) / N,  cb(j) = (c(j) * P) / N  (64-bit integer
+ *              division): P row blocks and P column blocks, contiguous id ranges balanced by nonzero count; empty blocks are legal.
+ *              Tile (a, b), id T = a * P + b, holds the nonzeros with rb(I[k]) = a and cb(J[k]) = b in ascending k; n_T of them.
+ *   schedule   sub-epoch s = the P tiles (a, (a + s) mod P), a = 0 .. P-1.  They share no focus row and no context row, so they
+ *              run concurrently (one wavefront each) without touching a common table row, and the tables end up, bit for bit, as
+ *              if the tiles had run one after another.  Sub-epochs are separate kernel launches: nothing else synchronises.
+ *   order      GE_SHUFFLE_NONE: sub-epochs s = 0 .. P-1, each tile in ascending k.  GE_SHUFFLE_DEVICE: the t-th sub-epoch run
+ *              is s = B(P, K(0))(t), and the q-th update of tile T is its B(n_T, K(T + 1))(q)-th nonzero, where
+ *                B(n, key)(x): b = the smallest b >= 0 with 2^b >= n, m = 2^b - 1, sh = b > 1 ? b / 2 : 1;  y = x;
+ *                              repeat  y = R(y)  until y < n;   R(y): for q = 0 .. 3 { y = (y + key[q]) & m;  y = (y * C[q]) & m;
+ *                              y ^= y >> sh },  C = { 0x9E3779B1, 0x85EBCA6B, 0xC2B2AE35, 0x27D4EB2F }  (32-bit unsigned);
+ *                K(salt):      z = seed * 0x9E3779B97F4A7C15 + (uint32) iteration * 0xD1B54A32D192ED03 + 0x632BE59BD9B4E019
+ *                              + salt * 0xA0761D6478BD642F  (mod 2^64);  for q = 0 .. 3 { z += 0x9E3779B97F4A7C15;  t = z;
+ *                              t = (t ^ (t >> 30)) * 0xBF58476D1CE4E5B9;  t = (t ^ (t >> 27)) * 0x94D049BB133111EB;
+ *                              t ^= t >> 31;  key[q] = the low 32 bits of t }.
+ *              GE_SHUFFLE_JAVA is GE_ERR_ARG: a global Fisher-Yates order cannot be stratified.
+ *              ge_glove_epoch_order returns the sequential equivalent: sub-epochs in the order they run, inside a sub-epoch
+ *              a ascending, inside a tile its walk.
+ *   cost       every tile is a job with its own fp32 accumulator starting at 0 (Adagrad.java:60); *cost_sum = the fp64 sum of
+ *              the tile costs in that same order.
+ *   P          cfg.strata, 1 <= P <= 2048; 0 = the largest power of two P with 8 * P * P <= N and P <= owned rows (at least 1,
+ *              at most 2048): a function of (rows, nnz) alone, never of the device.  A nonzero cfg.strata with another mode
+ *              is GE_ERR_ARG.
+ *   bound      an epoch takes ge_glove_info.strata_path = sum_s max_a n_(a, (a + s) mod P) sequential updates.  That is at least
+ *              the busiest row block and the busiest column block, and a single column with more than N / P nonzeros sets the
+ *              floor by itself, whatever P: 7.7 % of N on the 300-vertex Zipf test matrix, 1.0 % on the 100 k-vertex one (C2),
+ *              under 0.1 % on BCA-built matrices.  An epoch is at most P kernel launches (a sub-epoch without a nonzero is not
+ *              launched); measured: DESIGN.md 3.7.
+ *   fp32 rows only (bf16 is GE_ERR_ARG), plain tables as for DETERMINISTIC handles; threads, workers, the hub and the layout
+ *   fields are ignored; row_begin / row_end as for DETERMINISTIC (r and c count this handle's nonzeros). */
+enum { GE_MODE_HOGWILD = 0, GE_MODE_DETERMINISTIC = 1, GE_MODE_STRATIFIED = 2 };
 
 /* Order in which an epoch visits the nonzeros.
  * JAVA:   CoOccurrenceMatrix.shuffle() = cumulative forward Fisher-Yates on one permutation,
@@ -141,6 +174,7 @@ typedef struct {
     int32_t flush_every;    /* > 0: cut every hub run after this many updates instead (<= 128)              */
     int32_t blocks_per_cu;  /* > 0: workgroups of 4 workers per CU; default = what the occupancy API reports */
     int32_t layout_flags;   /* GE_LAYOUT_* below                                                            */
+    int32_t strata;         /* GE_MODE_STRATIFIED: P, 1 .. 2048; 0 = the default for (rows, nnz).  Must be 0 in every other mode */
 } ge_glove_cfg;
 
 /* ge_glove_cfg.layout_flags (GE_SHUFFLE_DEVICE handles).  Default 0: focus rows are packed whole into chunks, so a row
@@ -186,6 +220,8 @@ typedef struct {
     int32_t placements;       /* allocations tried for the record tables, both sides together (2 = no choice was made)              */
     float   placement_best_ms, placement_worst_ms;   /* probe times of the kept and of the slowest candidate, summed over the two sides */
     int32_t reserved_;
+    int32_t strata;           /* GE_MODE_STRATIFIED: the P in use (0 for the other modes)                                          */
+    int64_t strata_path;      /*   sum over sub-epochs of the largest tile: the epoch's length in sequential updates               */
 } ge_glove_info;
 
 
@@ -225,7 +261,8 @@ ge_status ge_glove_set_state(ge_glove *h, int32_t which, const float *in, int64_
  * ge_glove_info.row_stride floats).  bf16 row tables are refused (ge_glove_context_layout). */
 ge_status ge_glove_device_ptr(ge_glove *h, int32_t which, void **dptr, int64_t *count);
 
-/* The order in which ONE worker (cfg.workers = 1) walks the nonzeros in epoch `iteration` of a HOGWILD handle:
+/* GE_MODE_STRATIFIED handles: the sequential order the epoch equals (see GE_MODE_STRATIFIED).
+ * The order in which ONE worker (cfg.workers = 1) walks the nonzeros in epoch `iteration` of a HOGWILD handle:
  * out[k] = index into the caller's I/J/X of the k-th update.  With more workers the same chunks of 128 are
  * handed out in this order but run concurrently.  (GE_SHUFFLE_JAVA: the order of the most recent epoch.)
  * Lets a sequential implementation replay the device pass exactly (parity tests). */
@@ -638,6 +675,7 @@ const char *ge_version(void);
 /* sizeof(ge_glove_cfg) as the LIBRARY was compiled: a host built against another header revision must refuse to
  * run instead of letting ge_glove_cfg_default write past its struct. */
 int32_t ge_glove_cfg_size(void);
+int32_t ge_glove_info_size(void);      /* sizeof(ge_glove_info), same purpose */
 int32_t ge_bca_cfg_size(void);
 /* Diagnostic: the rate (GB/s, bytes read + written) of a plain 16-byte-per-lane device-to-device copy of `bytes` on this
  * device -- the practical ceiling bench.py prints beside a kernel's own rate (the boxes of a pool differ). */

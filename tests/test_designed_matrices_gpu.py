@@ -411,3 +411,120 @@ def test_cut_hub_runs_lose_no_update_with_many_workers(gpu, flush_every):
     # the other side: each focus row took exactly its one update (one fma onto 1), and the row nothing streams took none
     np.testing.assert_allclose(after["gsq_focus"][:col], rows, rtol=1e-6)
     assert np.array_equal(after["gsq_focus"][col], before["gsq_focus"][col])
+
+
+_FROZEN_TERMS = {}
+
+
+def _frozen_handle(V, I, J, X, xmax, D, dtype, **device):
+    """Learning rate 0 and the bias accumulators at 1e30, under the library's own worker count: nothing but the accumulator rows
+    moves, and every nonzero's weighted cost wc is a constant."""
+    cfg = make_config(D, "glove", mode="hogwild", shuffle="device", seed=42, learning_rate=0.0, dtype=dtype, **device)
+    opt = geglove.Adagrad(geglove.CooMatrix(V, I, J, X, xmax), cfg, cfg.costFunction())
+    opt.set_state("gsq_fbias", np.full(V, 1e30, np.float32)); opt.set_state("gsq_cbias", np.full(V, 1e30, np.float32))
+    return opt
+
+
+def _frozen_terms(key, before, I, J, X, xmax, vw, nch, resident_ctx):
+    """What the one resident row's accumulator must grow to (fp64 sum of the squared fp32 gradients, from 1) and what each streamed
+    row's accumulator becomes after its one fma, with the terms computed as the kernel computes them (kernel_model: its dot
+    product and cost terms).  Computed once per key; the tables it was computed from are kept to check that later callers share them."""
+    if key not in _FROZEN_TERMS:
+        F32, F64 = np.float32, np.float64
+        D = before["focus"].shape[1]
+        total = np.ones(D, F64)
+        streamed = np.ones((before["focus"].shape[0], D), F32)
+        for k in range(len(I)):
+            f, c = before["focus"][I[k]], before["context"][J[k]]
+            res, oth = (c, f) if resident_ctx else (f, c)
+            l, w = K.cost_terms(False, X[k], xmax)
+            dot = K.lane_dot(res, oth, vw, nch)
+            ic = F32(F64(dot) + (F64(F32(before["cbias"][J[k]] + before["fbias"][I[k]])) - l))
+            wc = F32(w * ic)
+            total += (wc * oth).astype(F32).astype(F64) ** 2
+            g = (wc * res).astype(F32)
+            o = I[k] if resident_ctx else J[k]
+            streamed[o] = K.fma32(g, g, streamed[o])
+        _FROZEN_TERMS[key] = (before, total, streamed)
+    first, total, streamed = _FROZEN_TERMS[key]
+    for name in before:
+        assert np.array_equal(before[name], first[name]), name
+    return total, streamed
+
+
+def _nothing_but_accumulators_moved(before, after, what):
+    for name in ("focus", "context", "fbias", "cbias", "gsq_fbias", "gsq_cbias"):
+        assert np.array_equal(after[name].view(np.uint32), before[name].view(np.uint32)), (what, name)
+
+
+@pytest.mark.parametrize("flush_every", [1, 4, 64])
+def test_cut_hub_runs_lose_no_update_with_many_workers_bf16(gpu, flush_every):
+    """test_cut_hub_runs_lose_no_update_with_many_workers with bf16 rows: the hub column lives in its fp32 master row, which the runs
+    read and publish into; the streamed focus rows are narrowed with stochastic rounding at every step, which on values bf16 already
+    holds (learning rate 0) must change nothing -- rows and biases keep their bits.  Same terms (the hub row is fp32, the focus rows
+    are what the bf16 table holds, vw = 4), same derived bound (count_j + 2 runs_j) 2^-24 on gradSqContext[j]; each focus row's
+    accumulator took exactly its one fma."""
+    D = 8
+    V, I, J, X, xmax = M.hub_column(3000)
+    col = 3000
+    opt = _frozen_handle(V, I, J, X, xmax, D, "bf16", hot="all", flush_every=flush_every)
+    info = opt.info()
+    assert info["flush_min"] == flush_every and info["hot_nonzeros"] == len(I)
+    assert info["runs"] >= -(-len(I) // flush_every)
+    assert (info["vector_width"], info["chunks_per_lane"]) == (4, 1)
+    before = _as2d(opt.state(), V, D)
+    assert np.all(before["focus"].view(np.uint32) & 0xFFFF == 0)                # what the bf16 table holds
+    opt.epoch(0)
+    after = _as2d(opt.state(), V, D)
+    opt.close()
+    _nothing_but_accumulators_moved(before, after, "bf16 hub column flush_every %d" % flush_every)
+    total, rows = _frozen_terms(("hub", "bf16"), before, I, J, X, xmax, 4, 1, True)
+    got = after["gsq_context"][col].astype(np.float64)
+    bound = (len(I) + 2 * info["runs"]) * 2.0 ** -24
+    rel = np.abs(got - total) / total
+    print("bf16 rows, flush_every %d, %d workers, %d runs: gradSq growth %.4f .. %.4f, relative error %.3g = %.4f of the bound %.3g (one update in %d is %.3g)"
+          % (flush_every, info["groups_in_flight"], info["runs"], (got - 1).min(), (got - 1).max(), rel.max(), rel.max() / bound, bound, len(I),
+             1.0 / len(I)))
+    assert info["groups_in_flight"] > 1
+    assert np.all(rel <= bound), (float(rel.max()), bound)
+    np.testing.assert_allclose(after["gsq_focus"][:col], rows[:col], rtol=1e-6)
+    assert np.array_equal(after["gsq_focus"][col:], before["gsq_focus"][col:])
+    keep = np.ones(V, bool); keep[col] = False
+    assert np.array_equal(after["gsq_context"][keep], before["gsq_context"][keep])
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_long_row_pieces_lose_no_update_with_many_workers(gpu, dtype):
+    """The transpose: one focus row of 3000 nonzeros, cut into 24 pieces (23 x 128 + 56) that many workers hold at once.  Each
+    piece publishes its accumulator delta with float atomics and the row itself by delta too -- atomics (fp32) or close_run()'s
+    read-modify-write (bf16 rows) -- so with learning rate 0 the row must keep its bits whatever the pieces do to each other, and
+    gradSqFocus[row] must grow by the sum over the row of (wc * context)^2.
+    Bound (derived as above, not tuned): per piece one fma per nonzero onto the accumulator in registers, one subtraction that forms
+    the delta, one atomic add that publishes it; every rounding is at most 2^-24 of a running value that never exceeds the final
+    total (a piece starts from what the others have published so far, and its own terms are not in that yet): relative error
+    <= (count + 2 pieces) 2^-24.  Each context row the row meets took exactly its one fma."""
+    D = 8
+    V, I, J, X, xmax = M.one_row(3000)
+    row = 3000
+    opt = _frozen_handle(V, I, J, X, xmax, D, dtype, hot="none")
+    info = opt.info()
+    pieces = -(-len(I) // 128)
+    assert info["hot_nonzeros"] == 0 and info["long_rows"] == 1 and info["shared_chunks"] == pieces
+    vw, nch = info["vector_width"], info["chunks_per_lane"]
+    before = _as2d(opt.state(), V, D)
+    opt.epoch(0)
+    after = _as2d(opt.state(), V, D)
+    opt.close()
+    _nothing_but_accumulators_moved(before, after, "%s long row" % dtype)
+    total, rows = _frozen_terms(("row", dtype), before, I, J, X, xmax, vw, nch, False)
+    got = after["gsq_focus"][row].astype(np.float64)
+    bound = (len(I) + 2 * pieces) * 2.0 ** -24
+    rel = np.abs(got - total) / total
+    print("%s rows, long row in %d pieces, %d workers: gradSq growth %.4f .. %.4f, relative error %.3g = %.4f of the bound %.3g (one update in %d is %.3g)"
+          % (dtype, pieces, info["groups_in_flight"], (got - 1).min(), (got - 1).max(), rel.max(), rel.max() / bound, bound, len(I), 1.0 / len(I)))
+    assert info["groups_in_flight"] > 1
+    assert np.all(rel <= bound), (float(rel.max()), bound)
+    np.testing.assert_allclose(after["gsq_context"][:row], rows[:row], rtol=1e-6)
+    assert np.array_equal(after["gsq_context"][row:], before["gsq_context"][row:])
+    keep = np.ones(V, bool); keep[row] = False
+    assert np.array_equal(after["gsq_focus"][keep], before["gsq_focus"][keep])

@@ -325,22 +325,8 @@ def test_rccl_path_runs_on_one_gpu(gpu):
     capi.check(capi.lib().ge_rccl_selftest(0))
 
 
-def _np_bf16_rne(x):
-    u = x.astype(np.float32).view(np.uint32).astype(np.uint64)
-    return (((u + 0x7FFF + ((u >> 16) & 1)) >> 16) & 0xFFFF).astype(np.uint16)
-
-
-def _np_bf16_to_f32(h):
-    return (h.astype(np.uint32) << 16).view(np.float32)
-
-
-def _np_mix32(x):
-    x = x.astype(np.uint64)
-    M = np.uint64(0xFFFFFFFF)
-    x ^= x >> np.uint64(15); x = (x * np.uint64(0x85EBCA77)) & M
-    x ^= x >> np.uint64(13); x = (x * np.uint64(0xC2B2AE3D)) & M
-    x ^= x >> np.uint64(16)
-    return x
+# (the numpy of this test lives in tests/exchange_ref.py, beside the rest of the exchange's model)
+from exchange_ref import narrow as _np_bf16_rne, widen as _np_bf16_to_f32, turn_bf16_rows as _np_turn_bf16_rows  # noqa: E402
 
 
 @pytest.mark.parametrize("pad", [0, 20])
@@ -375,18 +361,7 @@ def test_exchange_turn_bf16_matches_a_numpy_model(gpu, land, take, pad):
     d_t = torch.from_numpy(stored[:, :D].reshape(-1).copy().view(np.int16))
     # ---- model ----
     d = (t - b).astype(np.float32)
-    r = (_np_bf16_to_f32(w16) - _np_bf16_to_f32(o16)).astype(np.float32)
-    tn, bn = t.copy(), b.copy()
-    exp_t16, exp_hub = t16.copy(), hub.copy()
-    if land:
-        tn = (t + r).astype(np.float32)
-        bn = (b + r).astype(np.float32)
-        rnd = _np_mix32(((np.arange(V * D, dtype=np.uint64) * np.uint64(0x9E3779B1)) + np.uint64(seed)) & np.uint64(0xFFFFFFFF)) >> np.uint64(16)
-        stored16 = (((tn.view(np.uint32).astype(np.uint64) + rnd) >> np.uint64(16)) & np.uint64(0xFFFF)).astype(np.uint16)
-        exp_t16 = np.where(is_hub, t16, stored16)                          # hub rows: the bf16 copy is not touched
-        exp_hub[hpos] = tn[is_hub]
-    if take:
-        bn = (bn + _np_bf16_to_f32(_np_bf16_rne(d))).astype(np.float32)
+    exp_t16, exp_hub, bn, exp_own = _np_turn_bf16_rows(t16, hub, hub_index, D, b, w16, o16, land, take, seed)
     np.testing.assert_array_equal(back(d_t), exp_t16, err_msg="table")
     np.testing.assert_array_equal(back(d_b), bn, err_msg="base")
     np.testing.assert_array_equal(back(d_hub), exp_hub, err_msg="hub rows")

@@ -550,19 +550,29 @@ static ge_status similarity_pairs_impl(const ge_strings *strings, const int32_t 
     std::vector<uint8_t> dead;
     if (cfg->method == GE_SIM_NUMERIC) {
         dead.assign((size_t)n_src, 0);
-        // shortest non-empty target at or after each position
-        std::vector<int32_t> suffix_min((size_t)n_tgt + 1, INT32_MAX);
+        // A job skips its own vertex before it calls similarity (CompareJob.java:38), so a target kills job i only
+        // when it is non-empty, shorter than the job's '^' position, inside the job's range of targets and on ANOTHER
+        // vertex.  Per suffix of the targets: the shortest non-empty length, and the shortest on a second vertex;
+        // whichever of the two is not the job's own vertex is the shortest target the job reaches.
+        struct Shortest { int32_t len, vert, len_other; };
+        std::vector<Shortest> suffix((size_t)n_tgt + 1, Shortest{INT32_MAX, 0, INT32_MAX});
         for (int32_t j = n_tgt - 1; j >= 0; --j) {
-            const int32_t len = refs[(size_t)tgt[j]].len;
-            suffix_min[(size_t)j] = std::min(suffix_min[(size_t)j + 1], len > 0 ? len : INT32_MAX);
+            Shortest s = suffix[(size_t)j + 1];
+            const int32_t len = refs[(size_t)tgt[j]].len, v = tgt_vert[j];
+            if (len > 0) {
+                if (s.len == INT32_MAX || v == s.vert) s.len = std::min(s.len, len), s.vert = v;
+                else if (len < s.len) { s.len_other = s.len; s.len = len; s.vert = v; }
+                else s.len_other = std::min(s.len_other, len);
+            }
+            suffix[(size_t)j] = s;
         }
         for (int32_t i = 0; i < n_src; ++i) {
             const StrRef r = refs[(size_t)src[i]];
             const int hat = index_of(U + r.start, r.len, u'^');
             if (r.len == 0 || hat == -1) continue;
-            const int32_t from = cfg->upper_triangle ? i + 1 : 0;
-            // a shorter non-empty target differs from s1 and is another vertex, so the job reaches the substring
-            if (from <= n_tgt && suffix_min[(size_t)std::min(from, n_tgt)] < hat) dead[(size_t)i] = 1;
+            const Shortest &s = suffix[(size_t)std::min(cfg->upper_triangle ? i + 1 : 0, n_tgt)];
+            // a shorter non-empty target differs from s1, so a job that reaches it reaches the substring
+            if ((s.vert == src_vert[i] ? s.len_other : s.len) < hat) dead[(size_t)i] = 1;
         }
     }
 

@@ -418,7 +418,9 @@ int32_t ge_sim_pattern_supported(const char *pattern);
  * source_vertex / target_vertex the vertex ids (a job skips its own vertex, CompareJob.java:38).  The result lists
  * (i, j, (float) similarity) in job order -- i ascending, j ascending inside a job -- which is the order results
  * arrive in with `threads: 1`.  A Numeric job that dies in String.substring (Numeric.java:36) yields nothing, as its
- * ExecutionException does in the reference (Rdf2GrphConverter.java:176-178). */
+ * ExecutionException does in the reference (Rdf2GrphConverter.java:176-178).  A job dies when one of the targets it
+ * reaches -- at or after its start, on another vertex than its own -- is non-empty and shorter than the '^' position of
+ * the job's label; a short target on the job's own vertex is skipped before the substring and kills nothing. */
 ge_status ge_similarity_pairs(const ge_strings *strings,
                               const int32_t *source, const int32_t *source_vertex, int32_t n_source,
                               const int32_t *target, const int32_t *target_vertex, int32_t n_target,

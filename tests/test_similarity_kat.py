@@ -8,95 +8,13 @@ import numpy as np
 import pytest
 
 import oracle as O
+from sim_ref import py_cosine, py_jaccard, py_jaro_winkler, py_levenshtein, py_ngrams, py_tokens
 
 
 def sim(method, a, b, **kw):
     v, threw = O.sim_pair(O.sim_cfg(method, **kw), a, b)
     assert not threw
     return v
-
-
-# ---- independent Python models ---------------------------------------------------------------------------------
-def py_jaro_winkler(s1, s2):
-    f = np.float32
-    if s1 == s2:
-        return 1.0
-    mx, mn = (s1, s2) if len(s1) > len(s2) else (s2, s1)
-    rng = max(len(mx) // 2 - 1, 0)
-    flags = [False] * len(mx); idx = [-1] * len(mn)
-    for mi, c in enumerate(mn):
-        for xi in range(max(mi - rng, 0), min(mi + rng + 1, len(mx))):
-            if not flags[xi] and c == mx[xi]:
-                flags[xi] = True; idx[mi] = xi; break
-    ms1 = [mn[i] for i in range(len(mn)) if idx[i] != -1]
-    ms2 = [mx[i] for i in range(len(mx)) if flags[i]]
-    m = len(ms1)
-    if m == 0:
-        return 0.0
-    t = sum(a != b for a, b in zip(ms1, ms2)) // 2
-    prefix = 0
-    for a, b in zip(s1, s2):
-        if a != b:
-            break
-        prefix += 1
-    mf = f(m)
-    j = float(f(f(f(mf / f(len(s1))) + f(mf / f(len(s2)))) + f(f(mf - f(t)) / mf)) / f(3))
-    return j + min(0.1, 1.0 / len(mx)) * prefix * (1 - j) if j > 0.7 else j
-
-
-def py_levenshtein(a, b):
-    prev = list(range(len(b) + 1))
-    for i, ca in enumerate(a):
-        cur = [i + 1]
-        for j, cb in enumerate(b):
-            cur.append(min(cur[j] + 1, prev[j + 1] + 1, prev[j] + (ca != cb)))
-        prev = cur
-    return prev[-1]
-
-
-STOP = {"the", "of", "and", "a", "an", "to", "in", "is", "you", "that", "it", "for", "on", "from", "are", "as", "with", "at", "or", "by", "but", "if"}
-
-
-def py_tokens(s):
-    """Tokenator over UTF-16 code units (String.length / charAt / trim count units: an astral character is two)."""
-    u = [int(x) for x in O.utf16(s)]
-    stop = {tuple(ord(c) for c in w) for w in STOP}
-    out, start = {}, 0
-    for pos, ch in enumerate(u):
-        if ch == 32 or pos == len(u) - 1:
-            a, b = start, pos + 1
-            while a < b and u[a] <= 32: a += 1
-            while b > a and u[b - 1] <= 32: b -= 1
-            tok = tuple(u[a:b])
-            start = pos + 1
-            if len(tok) > 1 and tok not in stop:
-                out[tok] = out.get(tok, 0) + 1
-    return out
-
-
-def py_ngrams(s, k):
-    """k-grams over UTF-16 code units (java.lang.String.substring), whitespace runs collapsed first."""
-    u, t = [int(x) for x in O.utf16(s)], []
-    for c in u:
-        ws = c == 32 or 9 <= c <= 13
-        if ws and t and t[-1] == 32 and prev_ws:
-            continue
-        t.append(32 if ws else c); prev_ws = ws
-    out = {}
-    for i in range(len(t) - k + 1):
-        g = tuple(t[i:i + k]); out[g] = out.get(g, 0) + 1
-    return out
-
-
-def py_jaccard(p, q):
-    u = len(set(p) | set(q))
-    return (len(p) + len(q) - u) / u if u else float("nan")
-
-
-def py_cosine(p, q):
-    dot = sum(c * q.get(g, 0) for g, c in p.items())
-    n = np.sqrt(float(sum(c * c for c in p.values()))) * np.sqrt(float(sum(c * c for c in q.values())))
-    return dot / n if n else float("nan")
 
 
 # ---- known answers ---------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 // ge_glove_internal.h -- what the other translation units of libgeglove.so may ask of a trainer handle.  Defined in glove.hip
-// (struct ge_glove is private to it); used by sync.hip and pca.hip.
+// (struct ge_glove is private to it); used by sync.hip, pca.hip and eval.hip.
 #pragma once
 #include "ge_common.h"
 #include <vector>
@@ -31,5 +31,20 @@ const std::vector<int32_t> *glove_hub_columns(const ge_glove *h);
 const std::vector<int32_t> *glove_hub_counts(const ge_glove *h);
 // the columns this handle's epoch kernel treats as hubs (resident runs that publish the row and its accumulator row by float atomics)
 const std::vector<int32_t> *glove_kernel_hubs(const ge_glove *h);
+
+// Where eval.hip reads a handle's rows and biases, whichever layout the handle has (glove.hip `view_of`): row r of a table is
+// base + r * stride elements (fp32, or bf16 when emb16), a bias is bias[r * stride].  Focus-side tables start at row_begin (NOT
+// rebased: the reader subtracts it).  bf16 handles: column j's context row is hub32 + hub_index[j] * dim (fp32) when
+// hub_index[j] >= 0; hub_index is null when the handle keeps no masters.  Touches no device.
+struct EvalView {
+    const void *focus, *context;
+    const float *fbias, *cbias, *hub32;
+    const int32_t *hub_index;
+    int64_t focus_stride, context_stride, fbias_stride, cbias_stride;
+    double xmax;
+    int32_t vocab_size, dim, row_begin, row_end, cost_kind, emb16, device;
+    hipStream_t stream;
+};
+ge_status glove_eval_view(const ge_glove *h, EvalView *out);
 
 }  // namespace ge

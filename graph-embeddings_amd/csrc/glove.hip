@@ -1801,6 +1801,20 @@ ge_status glove_epoch_finish(ge_glove *h, double *cost_sum) {
     return GE_OK;
 }
 const std::vector<int32_t> *glove_hub_columns(const ge_glove *h) { return h ? &h->lay.heavy : nullptr; }
+ge_status glove_eval_view(const ge_glove *h, EvalView *out) {
+    if (!h) return ge::fail(GE_ERR_ARG, "null ge_glove handle");
+    const TableView foc = view_of(h, GE_STATE_FOCUS), ctx = view_of(h, GE_STATE_CONTEXT);
+    const TableView fb = view_of(h, GE_STATE_FBIAS), cb = view_of(h, GE_STATE_CBIAS);
+    out->focus = foc.base; out->context = ctx.base; out->focus_stride = foc.stride; out->context_stride = ctx.stride;
+    out->fbias = fb.first(); out->cbias = cb.first(); out->fbias_stride = fb.stride; out->cbias_stride = cb.stride;
+    out->emb16 = ctx.bf16 ? 1 : 0;
+    out->hub32 = ctx.bf16 && h->n_hub > 0 ? h->hub32 : nullptr;
+    out->hub_index = out->hub32 ? h->dhub_index : nullptr;
+    out->xmax = h->cfg.xmax; out->vocab_size = h->cfg.vocab_size; out->dim = h->cfg.dim;
+    out->row_begin = h->cfg.row_begin; out->row_end = h->cfg.row_begin + h->rows;
+    out->cost_kind = h->cfg.cost; out->device = h->cfg.device; out->stream = h->stream;
+    return GE_OK;
+}
 ge_status glove_sync_view(ge_glove *h, int32_t *opt, int32_t *mode, void **stream, int32_t *device) {
     if (!h) return ge::fail(GE_ERR_ARG, "null ge_glove handle");
     *opt = h->cfg.opt; *mode = h->cfg.mode; *stream = (void *)h->stream; *device = h->cfg.device;

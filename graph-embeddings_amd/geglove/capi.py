@@ -40,6 +40,7 @@ SYMBOLS = (
     "ge_nn_cfg_default", "ge_nn_cfg_size", "ge_nn_create", "ge_glove_nn_create", "ge_nn_query_rows", "ge_nn_query_vectors", "ge_nn_get",
     "ge_nn_last_kernel_ms", "ge_nn_destroy",
     "ge_synth_cfg_default", "ge_synth_cfg_size", "ge_synth_coo", "ge_coo_device", "ge_coo_synth_stats", "ge_glove_create_coo",
+    "ge_glove_eval_create", "ge_glove_eval_run", "ge_eval_last_kernel_ms", "ge_eval_get", "ge_eval_destroy", "ge_holdout_mask",
 )
 GE_NN_COSINE, GE_NN_DOT = 0, 1
 NN_METRICS = {"cosine": GE_NN_COSINE, "dot": GE_NN_DOT}
@@ -228,6 +229,7 @@ def lib():
     _declare_pca(L)
     _declare_nn(L)
     _declare_synth(L)
+    _declare_eval(L)
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int:      # default restype -> ge_status
@@ -520,6 +522,75 @@ def synth_coo(V, nnz, rows=None, seed=0xC0FFEE, device=0):
     h = C.c_void_p()
     check(lib().ge_synth_coo(C.byref(cfg), C.byref(h)))
     return Coo(h, V)
+
+
+def _declare_eval(L):
+    """The held-out evaluation section of include/geglove.h."""
+    vp, i32p, f32p, f64p = C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_double)
+    L.ge_glove_eval_create.argtypes = [vp, i32p, i32p, f32p, C.c_int64, C.POINTER(vp)]
+    L.ge_glove_eval_run.argtypes = [vp, f32p, f64p, f64p]
+    L.ge_eval_last_kernel_ms.argtypes = [vp, f32p]
+    L.ge_eval_get.argtypes = [vp, C.POINTER(C.c_int64), i32p]
+    L.ge_eval_destroy.argtypes = [vp]; L.ge_eval_destroy.restype = None
+    L.ge_holdout_mask.argtypes = [C.c_uint64, C.c_int64, C.c_double, C.POINTER(C.c_uint8)]
+
+
+class Evaluation:
+    """A ge_eval set on a trainer handle: Evaluation(glove_handle, I, J, X), then run() after any epoch.  Close it before the
+    trainer handle goes."""
+
+    def __init__(self, glove_handle, I, J, X):
+        import numpy as np
+        I = np.ascontiguousarray(I, dtype=np.int32); J = np.ascontiguousarray(J, dtype=np.int32)
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        if not (I.shape == J.shape == X.shape and I.ndim == 1):
+            raise ValueError("I, J, X must be one-dimensional arrays of one length")
+        i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        h = C.c_void_p()
+        check(lib().ge_glove_eval_create(glove_handle, I.ctypes.data_as(i32p), J.ctypes.data_as(i32p), X.ctypes.data_as(f32p),
+                                         I.shape[0], C.byref(h)))
+        self._h = h
+        self.n = I.shape[0]
+
+    def run(self, residual=True, term=True):
+        """(residual float32[n] or None, term float64[n] or None, cost_sum), the arrays in the caller's order."""
+        import numpy as np
+        res = np.empty(self.n, dtype=np.float32) if residual else None
+        trm = np.empty(self.n, dtype=np.float64) if term else None
+        total = C.c_double()
+        check(lib().ge_glove_eval_run(self._h, res.ctypes.data_as(C.POINTER(C.c_float)) if residual else None,
+                                      trm.ctypes.data_as(C.POINTER(C.c_double)) if term else None, C.byref(total)))
+        return res, trm, total.value
+
+    def kernel_ms(self):
+        ms = C.c_float()
+        check(lib().ge_eval_last_kernel_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    def reordered(self):
+        """True when creation sorted the set by focus row (it did not arrive so)."""
+        flag = C.c_int32()
+        check(lib().ge_eval_get(self._h, None, C.byref(flag)))
+        return bool(flag.value)
+
+    def close(self):
+        if self._h:
+            lib().ge_eval_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def holdout_mask(seed, n, fraction):
+    """ge_holdout_mask: uint8[n], 1 where nonzero k is held out (a function of seed, k and fraction alone; no device)."""
+    import numpy as np
+    mask = np.empty(n, dtype=np.uint8)
+    check(lib().ge_holdout_mask(int(seed) & 0xFFFFFFFFFFFFFFFF, n, float(fraction), mask.ctypes.data_as(C.POINTER(C.c_uint8))))
+    return mask
 
 
 def check(status):

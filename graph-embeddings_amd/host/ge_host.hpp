@@ -24,6 +24,7 @@
 #include <map>
 #include <set>
 #include <iterator>
+#include <limits>
 #include <condition_variable>
 #include <memory>
 #include <mutex>
@@ -260,7 +261,10 @@ struct Configuration {
              // off | apply: reduce the trained vectors to the leading components the `pca:` block asks for before they are written
              std::string pca = "off";
              // K > 0: after the vectors, write the K nearest kept vertices of every kept vertex to <name>.neighbors.tsv; cosine | dot
-             int neighbors = 0; std::string neighbors_metric = "cosine"; } device;
+             int neighbors = 0; std::string neighbors_metric = "cosine";
+             // F > 0: hold out that share of the nonzeros (ge_holdout_mask), train on the rest, report the held-out mean cost after
+             // every epoch and write <name>.holdout.tsv; held / total: the split's counts once the matrix is known (the banner shows them)
+             double holdout = 0; long long holdout_held = -1, holdout_total = -1; } device;
     std::vector<std::string> ignored_keys;     // legacy keys of the shipped YAMLs that the bean does not know
 
     int getThreads() const {       // Configuration.java:71-73
@@ -272,6 +276,9 @@ struct Configuration {
     bool usingPca() const { return pca.present; }
     bool applyingPca() const { return device.pca == "apply"; }
     bool writingNeighbors() const { return device.neighbors > 0; }
+    bool holdingOut() const { return device.holdout > 0; }
+    // the run's seed: `device.seed`, or the wall clock as Main seeds (Configuration.setThreadLocalRandom(), J/Main.java:62)
+    long long runSeed() const { return device.has_seed ? device.seed : (long long)(std::time(nullptr)) * 1000LL; }
     bool usingWeights() const { return has_weights && !weights.empty(); }
     bool usingSimilarity() const { return !similarity.empty(); }
 
@@ -354,6 +361,12 @@ struct Configuration {
                     else if (q.first == "pca") c.device.pca = q.second.scalar;
                     else if (q.first == "neighbors") c.device.neighbors = (int)num(&q.second);
                     else if (q.first == "neighbors_metric") c.device.neighbors_metric = q.second.scalar;
+                    else if (q.first == "holdout") {                                            // a number, all of it: anything else fails the check
+                        const std::string &t = q.second.scalar;
+                        char *end = nullptr;
+                        const double v = std::strtod(t.c_str(), &end);
+                        c.device.holdout = (q.second.kind == YNode::Scalar && !t.empty() && *end == 0) ? v : std::numeric_limits<double>::quiet_NaN();
+                    }
                     else if (q.first == "exchange") c.device.exchange = q.second.scalar;        // overlap | sync
                     else if (q.first == "transport") c.device.transport = q.second.scalar;      // auto | rccl | host
                     else if (q.first == "wire") c.device.wire = q.second.scalar;                // bf16 | f32
@@ -400,6 +413,8 @@ struct Configuration {
         if (c.device.strata != 0 && c.device.mode != "stratified") throw InvalidConfigurationException("device.strata needs device.mode: stratified");
         if (c.device.neighbors < 0 || c.device.neighbors > 128) throw InvalidConfigurationException("Invalid device.neighbors, choose a number from 1 to 128 (0 = off)");
         if (c.device.neighbors_metric != "cosine" && c.device.neighbors_metric != "dot") throw InvalidConfigurationException("Invalid device.neighbors_metric, choose one of: cosine, dot");
+        if (!(c.device.holdout >= 0 && c.device.holdout <= 0.5)) throw InvalidConfigurationException("Invalid device.holdout, choose a fraction from 0 to 0.5 (0 = off)");
+        if (c.holdingOut() && c.device.gpus > 1) throw InvalidConfigurationException("device.holdout runs on one rank only, set device.gpus: 1");
     }
 
     static std::string similarity_to_string(const std::map<std::string, std::string> &m) {     // SimilarityGroup.toString
@@ -441,6 +456,8 @@ struct Configuration {
         } else L.push_back("No similarity matching will be performed");
         if (device.mode == "stratified") L.push_back("Stratified trainer: " + (device.strata > 0 ? std::to_string(device.strata) + " strata" : std::string("strata chosen from the matrix")));
         if (writingNeighbors()) L.push_back("Nearest neighbours: " + std::to_string(device.neighbors) + " (" + device.neighbors_metric + ")");
+        if (holdingOut()) L.push_back("Holdout: " + java_number(device.holdout, false) + (device.holdout_total < 0 ? std::string() :
+                                      " (" + std::to_string(device.holdout_held) + " of " + std::to_string(device.holdout_total) + " nonzeros)"));
         return L;
     }
 };
@@ -934,6 +951,45 @@ private:
     std::vector<int32_t> I_, J_; std::vector<float> X_; double max_ = 0;
 };
 
+// `device: { holdout: F }`: the matrix the trainer sees -- the nonzeros ge_holdout_mask(seed, N, F) keeps, in matrix order, with the
+// FULL matrix's max() and the unchanged vocabulary -- and the held-out nonzeros beside it (heldI / heldJ / heldX, matrix order).
+class HoldoutMatrix : public CoOccurrenceMatrix {
+public:
+    HoldoutMatrix(const CoOccurrenceMatrix &full, uint64_t seed, double fraction) : full_(full) {
+        const int64_t N = full.coOccurrenceCount();
+        std::vector<uint8_t> mask((size_t)N);
+        check(ge_holdout_mask(seed, N, fraction, mask.data()));
+        const int32_t *I = full.dataI(), *J = full.dataJ(); const float *X = full.dataX();
+        for (int64_t k = 0; k < N; ++k) {
+            const bool held = mask[(size_t)k] != 0;
+            (held ? hI_ : I_).push_back(I[k]); (held ? hJ_ : J_).push_back(J[k]); (held ? hX_ : X_).push_back(X[k]);
+        }
+        const std::string of = " of the " + std::to_string(N) + " nonzeros";
+        if (I_.empty()) throw std::runtime_error("device.holdout: " + java_number(fraction, false) + " leaves none" + of + " to train on");
+        if (hI_.empty()) throw std::runtime_error("device.holdout: " + java_number(fraction, false) + " holds out none" + of + ", nothing to evaluate");
+    }
+    int vocabSize() const override { return full_.vocabSize(); }
+    double max() const override { return full_.max(); }
+    std::string getKey(int index) const override { return full_.getKey(index); }
+    int8_t getType(int index) const override { return full_.getType(index); }
+    int cIdx_I(int i) const override { return I_[(size_t)i]; }
+    int cIdx_J(int j) const override { return J_[(size_t)j]; }
+    float cIdx_C(int i) const override { return X_[(size_t)i]; }
+    int coOccurrenceCount() const override { return (int)I_.size(); }
+    void shuffle() override {}
+    const int32_t *dataI() const override { return I_.data(); }
+    const int32_t *dataJ() const override { return J_.data(); }
+    const float *dataX() const override { return X_.data(); }
+    int64_t heldCount() const { return (int64_t)hI_.size(); }
+    const int32_t *heldI() const { return hI_.data(); }
+    const int32_t *heldJ() const { return hJ_.data(); }
+    const float *heldX() const { return hX_.data(); }
+private:
+    const CoOccurrenceMatrix &full_;
+    std::vector<int32_t> I_, J_, hI_, hJ_;
+    std::vector<float> X_, hX_;
+};
+
 // ------------------------------------------------------------------------------------------------
 // Optimizer
 // ------------------------------------------------------------------------------------------------
@@ -941,6 +997,7 @@ struct Optimum {                                 // J/opt/Optimum.java
     double finalCost = 0;
     std::vector<double> result;
     std::vector<double> costHistory;
+    std::vector<double> holdoutHistory;          // `device.holdout`: the held-out mean cost after every epoch (else empty)
 };
 struct IOptimizer {                              // J/opt/IOptimizer.java:6-11
     virtual ~IOptimizer() = default;
@@ -948,6 +1005,10 @@ struct IOptimizer {                              // J/opt/IOptimizer.java:6-11
     virtual std::string getName() const = 0;
     virtual std::vector<double> extractResult() = 0;
     virtual std::string scheduleNote() const { return std::string(); }      // what the library decided, for the log ("" = nothing to say)
+    // `device.holdout`: evaluate these nonzeros after every epoch (ge_glove_eval_*); the arrays may go when this returns
+    virtual void holdOut(const int32_t *, const int32_t *, const float *, int64_t) { throw std::invalid_argument("this optimizer evaluates no held-out nonzeros"); }
+    // the held-out mean cost after the epoch the progress callback is being told about; NaN without a held-out set
+    virtual double lastHoldoutCost() const { return std::numeric_limits<double>::quiet_NaN(); }
 };
 enum class CostFunction { GLOVE, PGLOVE };       // GloveCost / PGloveCost
 
@@ -967,7 +1028,7 @@ public:
         cfg.xmax = m.max();
         cfg.threads = config.getThreads();
         // Main seeds from the wall clock (Configuration.setThreadLocalRandom(), J/Main.java:62); `device.seed` pins it
-        cfg.seed = config.device.has_seed ? config.device.seed : (long long)(std::time(nullptr)) * 1000LL;
+        cfg.seed = config.runSeed();
         cfg.mode = config.device.mode == "deterministic" ? GE_MODE_DETERMINISTIC : config.device.mode == "stratified" ? GE_MODE_STRATIFIED : GE_MODE_HOGWILD;
         cfg.strata = config.device.strata;
         cfg.shuffle = config.device.shuffle == "java" ? GE_SHUFFLE_JAVA : config.device.shuffle == "none" ? GE_SHUFFLE_NONE : GE_SHUFFLE_DEVICE;
@@ -999,6 +1060,12 @@ public:
             check(ge_glove_epoch(h_.get(), iteration, &localCost));
             localCost = localCost / coCount_;
             opt.costHistory.push_back(localCost);
+            if (eval_) {                          // the tolerance stop stays on the training cost
+                double held = 0;
+                check(ge_glove_eval_run(eval_.get(), nullptr, nullptr, &held));
+                lastHoldout_ = held / (double)nHeld_;
+                opt.holdoutHistory.push_back(lastHoldout_);
+            }
             const double iterDiff = std::fabs(prevCost - localCost);
             if (progress_) progress_(iteration, localCost, iterDiff);
             prevCost = localCost;
@@ -1008,6 +1075,12 @@ public:
         opt.finalCost = finalCost;
         return opt;
     }
+    void holdOut(const int32_t *I, const int32_t *J, const float *X, int64_t n) override {
+        ge_eval *e = nullptr;
+        check(ge_glove_eval_create(h_.get(), I, J, X, n, &e));
+        eval_.reset(e); nHeld_ = n;
+    }
+    double lastHoldoutCost() const override { return lastHoldout_; }
     std::vector<double> extractResult() override {
         std::vector<double> out((size_t)vocab_ * (size_t)dim_);
         check(ge_glove_extract_f64(h_.get(), out.data()));
@@ -1015,7 +1088,11 @@ public:
     }
 private:
     struct Del { void operator()(ge_glove *g) const { ge_glove_destroy(g); } };
+    struct DelEval { void operator()(ge_eval *e) const { ge_eval_destroy(e); } };
     std::unique_ptr<ge_glove, Del> h_;
+    std::unique_ptr<ge_eval, DelEval> eval_;      // declared after h_: destroyed before the handle it reads
+    int64_t nHeld_ = 0;
+    double lastHoldout_ = std::numeric_limits<double>::quiet_NaN();
     int coCount_, vocab_, dim_, maxIter_;
     double tolerance_;
     void (*progress_)(int, double, double);
@@ -1275,6 +1352,22 @@ inline std::string writeNeighbors(const Configuration &config, const Optimum &op
         out.write(line.data(), (std::streamsize)line.size());
     }
     return "wrote " + std::to_string(K) + " " + config.device.neighbors_metric + " neighbours of " + std::to_string(kept) + " vertices to " + outputFolder + "/" + file;
+}
+
+// `device: { holdout: F }`: <fileName>.holdout.tsv carries the banner, then one line per epoch: the iteration as ge_glove_epoch
+// counts it (from 0), the training mean cost and the held-out mean cost, both as %.17g (text that parses back to the same double).
+inline std::string writeHoldout(const Configuration &config, const Optimum &optimum, const std::string &fileName, const std::string &outputFolder) {
+    std::filesystem::create_directories(outputFolder);
+    const std::string file = fileName + ".holdout.tsv";
+    std::ofstream out(outputFolder + "/" + file);
+    if (!out) throw std::runtime_error("cannot open " + file + " in " + outputFolder);
+    for (auto &l : config.banner()) out << "# " << l << "\n";
+    char b[96];
+    for (size_t it = 0; it < optimum.holdoutHistory.size(); ++it) {
+        std::snprintf(b, sizeof b, "%zu\t%.17g\t%.17g\n", it, optimum.costHistory[it], optimum.holdoutHistory[it]);
+        out << b;
+    }
+    return "wrote " + std::to_string(optimum.holdoutHistory.size()) + " epochs to " + outputFolder + "/" + file;
 }
 
 // ------------------------------------------------------------------------------------------------

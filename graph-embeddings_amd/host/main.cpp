@@ -1,6 +1,6 @@
 // geglove -c <config.yml> : the reference's CLI (J/Main.java:133-160) over the MI355X library.
 // Same single flag, same settings banner, same output files ./out/<name>.{vectors,dict}.tsv
-// (and <name>.neighbors.tsv with `device: { neighbors: K }`).
+// (and <name>.neighbors.tsv with `device: { neighbors: K }`, <name>.holdout.tsv with `device: { holdout: F }`).
 #include <ctime>
 #include "ge_host.hpp"
 
@@ -27,13 +27,17 @@ static void log_error(const std::string &msg) {
     std::fprintf(stderr, "%s %-5s %-25s :: %s\n", ts, "ERROR", "Graph Embeddings", msg.c_str());
 }
 static double g_tolerance = 0;
+static const IOptimizer *g_optimizer = nullptr;          // the run's optimizer, for the held-out cost beside the training cost
 static void progress(int iteration, double cost, double diff) {
-    char b[160];
-    std::snprintf(b, sizeof b, "epoch %d  cost %.9g  %.6g/%.6g", iteration + 1, cost, diff, g_tolerance);
+    char b[200];
+    const double held = g_optimizer ? g_optimizer->lastHoldoutCost() : std::nan("");
+    if (held == held) std::snprintf(b, sizeof b, "epoch %d  cost %.9g  holdout %.9g  %.6g/%.6g", iteration + 1, cost, held, diff, g_tolerance);
+    else std::snprintf(b, sizeof b, "epoch %d  cost %.9g  %.6g/%.6g", iteration + 1, cost, diff, g_tolerance);
     log_info("Optimizer", b);
 }
 
-static void runProgram(const Configuration &config) {                       // J/Main.java:29-78
+static void runProgram(const Configuration &given) {                        // J/Main.java:29-78
+    Configuration config = given;               // `device.holdout` pins the seed and learns the split's counts below
     for (auto &l : config.banner()) log_info("Graph Embeddings", l);
     for (auto &k : config.ignored_keys) log_info("Configuration", "ignoring key not known to this revision's bean: " + k);
     std::string outFileName = config.output.name;
@@ -62,14 +66,22 @@ static void runProgram(const Configuration &config) {                       // J
             log_info("BookmarkColoring", "wrote COO checkpoint " + config.device.save_coo);
         }
     }
-    const CoOccurrenceMatrix &bca = *matrix;
     {
         char b[200];
-        std::snprintf(b, sizeof b, "BCA: %d co-occurrences, max %.9g", bca.coOccurrenceCount(), bca.max());
+        std::snprintf(b, sizeof b, "BCA: %d co-occurrences, max %.9g", matrix->coOccurrenceCount(), matrix->max());
         log_info("BookmarkColoring", b);
     }
+    std::unique_ptr<HoldoutMatrix> split;
+    if (config.holdingOut()) {
+        config.device.seed = config.runSeed(); config.device.has_seed = true;      // one seed for the split and the trainer
+        split.reset(new HoldoutMatrix(*matrix, (uint64_t)config.device.seed, config.device.holdout));
+        config.device.holdout_held = split->heldCount(); config.device.holdout_total = matrix->coOccurrenceCount();
+        log_info("Graph Embeddings", config.banner().back());
+    }
+    const CoOccurrenceMatrix &bca = split ? static_cast<const CoOccurrenceMatrix &>(*split) : *matrix;
     g_tolerance = config.opt.tolerance;
     std::unique_ptr<IOptimizer> optimizer = createOptimizer(config, bca, progress);
+    if (split) { optimizer->holdOut(split->heldI(), split->heldJ(), split->heldX(), split->heldCount()); g_optimizer = optimizer.get(); }
     if (!optimizer->scheduleNote().empty()) log_info("Optimizer", optimizer->scheduleNote());
     Optimum optimum = optimizer->optimize();
     {
@@ -81,12 +93,14 @@ static void runProgram(const Configuration &config) {                       // J
     EmbeddingTextWriter writer(outFileName, config);
     const long long n = writer.write(optimum, bca, "out");
     log_info("EmbeddingTextWriter", "wrote " + std::to_string(n) + " vectors to out/" + writer.vectorsFile());
+    if (split) log_info("Holdout", writeHoldout(config, optimum, outFileName, "out"));
     if (config.writingNeighbors()) {
         std::string warning;
         const std::string done = writeNeighbors(config, optimum, bca, outFileName, "out", warning);
         if (!warning.empty()) log_warn("Neighbors", warning);
         log_info("Neighbors", done);
     }
+    g_optimizer = nullptr;
 }
 
 int main(int argc, char **argv) {

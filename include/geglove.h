@@ -671,6 +671,42 @@ ge_status ge_nn_get(const ge_nn *p, int64_t *n_indexed, int32_t *dim, int32_t *m
 ge_status ge_nn_last_kernel_ms(const ge_nn *p, float *prepare_ms, float *query_ms);
 void      ge_nn_destroy(ge_nn *p);
 
+/* ------------------------------------------------------------------------------------------
+ * Held-out evaluation: how well do the vectors predict co-occurrences the trainer never saw?  The cost term of
+ * Adagrad.createJob (J/opt/grad/Adagrad.java:60-75), computed and not applied, for a set of nonzeros (I[k], J[k], X[k]),
+ * k = 0 .. n-1, that need not be the handle's own: arbitrary pairs, read from whichever layout the handle keeps its tables in
+ * (plain tables, records, packed records, bf16 rows with fp32 hub masters, a shard).  The arithmetic is the bit-exact
+ * trainer's (csrc/ge_exact.h exact_update), stopped before the update:
+ *   s          the fp32 sum over ascending d of the fp32 products focus[i][d] * context[j][d]; products not fused, sum from 0.0f.
+ *   l, w       cost_terms<true> (csrc/ge_cost.h) with the handle's cost kind and the handle's xmax.
+ *   residual   ic = (float)((double)s + ((double)(fBias[i] + cBias[j]) - l));  wc = w * ic.
+ *   term       t_k = (0.5 * (double)wc) * (double)ic, an fp64 value: what the exact kernel adds to its job accumulator.
+ *   cost_sum   fp64, over a fixed partition: S_b = the sum of t_k over k in [1024 b, 1024 (b + 1)) in ascending k, from 0.0;
+ *              cost_sum = the sum of S_b in ascending b, from 0.0.  No floating-point atomics: the same input gives the same
+ *              bytes on every run and every machine.
+ *   bf16       a row is read where the handle keeps it: the fp32 master row when hub_index[j] >= 0, else the bf16 entry widened
+ *              exactly; from there the same arithmetic.
+ *   pure read  no table is written; neither the RNG state nor the permutation is touched.
+ * Limits, checked on the host before any device work (GE_ERR_ARG): 1 <= n < 2^31; I[k] inside the handle's owned rows
+ * [row_begin, row_end); J[k] in [0, V); X[k] finite and > 0, and < 1 for pGloVe; no null argument.
+ * The set is a handle of its own (evaluated after every epoch, uploaded once).  Creation may reorder the set by focus row so
+ * that consecutive nonzeros share rows; results always come back in the caller's k order and cost_sum follows the partition
+ * above in the caller's k.  ge_glove_eval_run runs on the trainer handle's stream and is blocking, like every call on a handle.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct ge_eval ge_eval;
+ge_status ge_glove_eval_create(ge_glove *h, const int32_t *I, const int32_t *J, const float *X, int64_t n, ge_eval **out);
+/* out_residual: HOST float[n] or NULL; out_term: HOST double[n] or NULL; both in the caller's k order.  cost_sum may be NULL. */
+ge_status ge_glove_eval_run(ge_eval *e, float *out_residual, double *out_term, double *cost_sum);
+/* Device time of the last run's kernels (hipEvents around them; copies not counted), in milliseconds; 0 = none ran. */
+ge_status ge_eval_last_kernel_ms(const ge_eval *e, float *ms);
+/* *n = nonzeros of the set; *reordered = 1 when creation sorted it by focus row (0: it arrived so).  Either may be NULL. */
+ge_status ge_eval_get(const ge_eval *e, int64_t *n, int32_t *reordered);
+void      ge_eval_destroy(ge_eval *e);     /* before the ge_glove it was created for */
+/* The split rule, HOST ONLY (no device): mask[k] = 1 when nonzero k is held out, i.e. when
+ * hi(SM(seed ^ 0x484F4C444F5554, k)) < T, T = floor(fraction * 2^32) computed in fp64 (SM, hi: the notation of the synthetic
+ * matrix above).  A function of (seed, k, fraction) alone.  fraction outside (0, 0.5] (NaN included): GE_ERR_ARG. */
+ge_status ge_holdout_mask(uint64_t seed, int64_t n, double fraction, uint8_t *mask);
+
 /* ------------------------------------------------------------------------------------------ */
 const char *ge_last_error(void);     /* message of the calling thread's last failed call */
 const char *ge_version(void);

@@ -86,7 +86,7 @@ struct BcaParams {
     unsigned long long *pool_used;     // bump allocator
     unsigned long long *queue;         // next bookmark
     unsigned long long *prof;          // GE_BCA_TIMING: [0] shader-clock ticks spent in the passes, [1] in the emission, summed over the wavefronts (else null)
-    int32_t *status;                   // 0 ok, 1 table overflow, 2 active-list overflow, 3 pool overflow
+    int32_t *status;                   // bit k set: some bookmark of the launch ended with status k -- 1 table overflow, 2 active-list overflow, 3 pool overflow, 4 outgrew the LDS tables
     const int32_t *redo;               // second launch: the bookmarks (relative to row_begin) whose rows did not fit
     int32_t n_jobs;                    // number of jobs in this launch (all rows, or the redo list)
 };
@@ -518,7 +518,7 @@ __global__ __launch_bounds__(64) void k_bca(BcaParams p) {
         status = rfl(status);
         const unsigned long long t_passes = p.prof ? __builtin_amdgcn_s_memtime() : 0ull;
         if (LDS && !ok && status == 4) {                   // outgrew the LDS tables: the global-memory kernel runs this bookmark
-            if (lane == 0) { p.row_n[r] = 0; p.row_off[r] = -2; p.row_max[r] = 1.0f; atomicMax(p.status, 4); }
+            if (lane == 0) { p.row_n[r] = 0; p.row_off[r] = -2; p.row_max[r] = 1.0f; atomicOr(p.status, 1 << 4); }
             for (int i = lane; i < LDS_HC; i += 64) s_hkey[i] = KEY_EMPTY;
             wave_sync();
             continue;
@@ -665,7 +665,7 @@ __global__ __launch_bounds__(64) void k_bca(BcaParams p) {
             bool fits = true;
             if (off + n_out > p.out_cap) { fits = false; }      // the row size is known: it is re-run alone into an exact pool
             if (!fits) {
-                if (lane == 0) { p.row_n[r] = n_out; p.row_off[r] = -1; p.row_max[r] = 1.0f; atomicMax(p.status, 3); }
+                if (lane == 0) { p.row_n[r] = n_out; p.row_off[r] = -1; p.row_max[r] = 1.0f; atomicOr(p.status, 1 << 3); }
                 if constexpr (LDS) { for (int i = lane; i < LDS_HC; i += 64) s_hkey[i] = KEY_EMPTY; }       // (the emission has used the LDS)
                 else { for (int e = lane; e < n_touched && e < p.hc / 2; e += 64) w.hkey[w.touched[e]] = KEY_EMPTY; }
                 wave_sync();
@@ -781,7 +781,7 @@ __global__ __launch_bounds__(64) void k_bca(BcaParams p) {
             p.row_n[r] = ok ? n_out : 0;
             p.row_off[r] = (LDS && !ok) ? -2 : off;                   // (the LDS kernel's tables do not grow: the other kernel takes the row)
             p.row_max[r] = row_max;
-            if (!ok) atomicMax(p.status, LDS ? 4 : (status ? status : 1));
+            if (!ok) atomicOr(p.status, 1 << (LDS ? 4 : (status ? status : 1)));
         }
         if (p.prof && lane == 0) {
             const unsigned long long t_end = __builtin_amdgcn_s_memtime();
@@ -936,8 +936,12 @@ static ge_status ge_bca_build_impl(const ge_csr *out_nbrs, const ge_csr *in_nbrs
     // bookmarks that outgrew the LDS tables (status 4, size unknown).  Those are run by the global-memory kernel (k_bca<false>,
     // tables that grow on overflow): first without a pool, to learn their sizes, then -- together with the rows the pool had no
     // room for -- into a second pool of exactly the missing size.  cfg.table_slots > 0 (tests) or GE_BCA_TABLES=global: the
-    // global-memory kernel does everything, as before round 3.
+    // global-memory kernel does everything, as before round 3.  GE_BCA_WAVES=n (n >= 1) caps the wavefronts of every launch (it never
+    // raises them): with 1, one wavefront runs the bookmarks of a launch in ascending order, so which row follows which on a
+    // wavefront's tables, and which rows the pool refuses, no longer depends on scheduling (tests).
     const char *tables_env = std::getenv("GE_BCA_TABLES");
+    int64_t waves_cap = 0;
+    if (const char *ev = std::getenv("GE_BCA_WAVES")) waves_cap = std::atoll(ev);
     const bool use_lds = cfg->table_slots == 0 && !(tables_env && std::strcmp(tables_env, "global") == 0);
     // global-memory tables: the TreeMap never holds more than 1/epsilon nodes (every node in it carries >= epsilon of at most 1.0
     // paint); the table holds every node touched by the forward+reverse passes.  Both grow on overflow.
@@ -962,6 +966,7 @@ static ge_status ge_bca_build_impl(const ge_csr *out_nbrs, const ge_csr *in_nbrs
         w.stride = (work_bytes(w.hc, w.ac) + 255) / 256 * 256;
         w.n_waves = std::min<int64_t>((int64_t)cus * (lds ? 10 : 16), n_rows);
         while (w.n_waves > 1 && w.n_waves * w.stride > (int64_t)6 << 30) w.n_waves /= 2;
+        if (waves_cap >= 1) w.n_waves = std::min(w.n_waves, waves_cap);
         if (hipMalloc((void **)&w.mem, (size_t)(w.n_waves * w.stride)) != hipSuccess) {
             (void)hipGetLastError(); w.mem = nullptr;
             return ge::fail(GE_ERR_OOM, "device allocation failed for BCA work buffers (table %lld slots x %lld waves)", (long long)w.hc, (long long)w.n_waves);
@@ -984,13 +989,20 @@ static ge_status ge_bca_build_impl(const ge_csr *out_nbrs, const ge_csr *in_nbrs
         if (e == hipSuccess) e = hipDeviceSynchronize();
         if (e == hipSuccess) e = hipMemcpy(h_ctr, d_ctr, 32, hipMemcpyDeviceToHost);
         if (e != hipSuccess) return ge::fail(GE_ERR_HIP, "BCA kernel failed: %s", hipGetErrorString(e));
-        *status = (int32_t)(h_ctr[2] & 0xFFFFFFFFull); *used = h_ctr[0];
+        // One status per launch, the one that must be acted on first.  A bookmark whose tables overflowed left no row and no size:
+        // only growing the tables and running the launch again brings it back, whatever else happened in the same launch -- a row
+        // the pool refused (3) is re-run by size, and a maximum over the codes let that 3 hide the 1 beside it.
+        const uint32_t bits = (uint32_t)(h_ctr[2] & 0xFFFFFFFFull);
+        *status = bits & (1u << 1) ? 1 : bits & (1u << 2) ? 2 : bits & (1u << 4) ? 4 : bits & (1u << 3) ? 3 : 0;
+        *used = h_ctr[0];
         return GE_OK;
     };
     struct Guard { std::function<void()> f; ~Guard() { f(); } };
     Work wmain, wglob;
     Guard work_guard{[&] { free_work(wmain); free_work(wglob); }};
-    auto grow = [&](int32_t status) { if (status == 1) hc *= 4; else ac = std::min<int64_t>(ac * 4, (int64_t)V + 64); };
+    int n_grow = 0;                // what the path report of GE_BCA_TIMING counts
+    size_t n_big = 0, n_refused = 0;
+    auto grow = [&](int32_t status) { ++n_grow; if (status == 1) hc *= 4; else ac = std::min<int64_t>(ac * 4, (int64_t)V + 64); };
 
     // the result object exists from here on: its host arrays are sized from the sample and their pages touched while the main launch runs
     std::unique_ptr<ge_coo> cown(new (std::nothrow) ge_coo());
@@ -1052,6 +1064,7 @@ static ge_status ge_bca_build_impl(const ge_csr *out_nbrs, const ge_csr *in_nbrs
         GE_HIP(hipMemcpy(h_off.data(), d_row_off, sizeof(int64_t) * (size_t)n_rows, hipMemcpyDeviceToHost));
         std::vector<int32_t> redo, big;
         for (int32_t r = 0; r < n_rows; ++r) if (h_off[(size_t)r] < 0) { redo.push_back(r); if (h_off[(size_t)r] == -2) big.push_back(r); }
+        n_big = big.size(); n_refused = redo.size() - big.size();
         int32_t *d_redo = nullptr;
         GE_HIP(hipMalloc((void **)&d_redo, sizeof(int32_t) * std::max<size_t>(redo.size(), 1))); dev.keep(d_redo);
         const Work *wredo = &wmain;
@@ -1082,6 +1095,9 @@ static ge_status ge_bca_build_impl(const ge_csr *out_nbrs, const ge_csr *in_nbrs
         }
         if (status != 0) return ge::fail(GE_ERR_OVERFLOW, "BCA second pool overflowed (internal sizing error, status %d)", status);
     }
+    if (clk.on)     // which path the rows took: a test that means to exercise the hand-over, the re-run or the table growth can see that it did
+        std::fprintf(stderr, "[ge_bca_build] rows %d: handed over %zu (LDS bounds), re-run for the pool %zu, table growths %d, tables %s\n",
+                     n_rows, n_big, n_refused, n_grow, use_lds ? "lds" : "global");
     clk.lap("upload + k_bca passes");
 
     for (auto &th : prefault) th.join();

@@ -9,6 +9,7 @@
 // The layout (two histograms, two scans, a stable counting sort of the nonzeros by tile) is built on the HOST, once per handle:
 // it is O(N + V + P^2) of plain loops over arrays the host already holds, paid at create time.
 // Compiled with -ffp-contract=off like every user of ge_exact.h.
+// A handle whose arithmetic is GE_ARITH_FP32 launches k_strata_fp32 (strata_fp32.hip) on the same schedule instead.
 #include "ge_strata.h"
 
 #include <algorithm>
@@ -16,33 +17,6 @@
 
 namespace ge {
 namespace {
-
-// SplitMix64 of (seed, iteration, salt) -> four round keys of bij_mix.  salt 0: the sub-epoch order; tile id + 1: that tile's walk.
-// (salt 0 gives the keys of the DETERMINISTIC mode's nonzero bijection, glove.hip bijection_keys.)
-__host__ __device__ __forceinline__ void strata_keys(int64_t seed, int32_t iteration, uint32_t salt, uint32_t key[4]) {
-    uint64_t z = (uint64_t)seed * 0x9E3779B97F4A7C15ULL + (uint64_t)(uint32_t)iteration * 0xD1B54A32D192ED03ULL + 0x632BE59BD9B4E019ULL
-               + (uint64_t)salt * 0xA0761D6478BD642FULL;
-    for (int q = 0; q < 4; ++q) {
-        z += 0x9E3779B97F4A7C15ULL;
-        uint64_t t = z;
-        t = (t ^ (t >> 30)) * 0xBF58476D1CE4E5B9ULL;
-        t = (t ^ (t >> 27)) * 0x94D049BB133111EBULL;
-        t ^= t >> 31;
-        key[q] = (uint32_t)t;
-    }
-}
-// the bijection permutes [0, 2^bits), the smallest power of two that covers n (n >= 1)
-__host__ __device__ __forceinline__ void strata_width(uint32_t n, uint32_t *mask, uint32_t *shift) {
-    uint32_t bits = 0;
-    while (bits < 31 && (1u << bits) < n) ++bits;
-    *mask = (1u << bits) - 1u;
-    *shift = bits > 1 ? bits / 2 : 1;
-}
-// position x of a keyed bijection of [0, n), cycle-walked (2^bits < 2n: fewer than two rounds expected)
-__host__ __device__ __forceinline__ uint32_t strata_walk(uint32_t x, uint32_t n, uint32_t mask, uint32_t shift, const uint32_t key[4]) {
-    do { x = bij_mix(x, mask, shift, key); } while (x >= n);
-    return x;
-}
 
 // One wavefront per tile: workgroup a of sub-epoch `sub` walks tile (a, (a + sub) mod P) in order and writes its fp32 cost.
 // LDS: dim floats (the product row of exact_update).  An empty tile returns at once (its cost stays the 0 of create time).
@@ -80,8 +54,8 @@ void sub_epoch_order(int32_t P, int64_t seed, int32_t iteration, bool shuffle, s
 }  // namespace
 
 void Strata::release() {
-    for (void *q : {(void *)dI, (void *)dJ, (void *)dX, (void *)dtoff, (void *)dcost}) if (q) (void)hipFree(q);
-    dI = dJ = dtoff = nullptr; dX = dcost = nullptr;
+    for (void *q : {(void *)dI, (void *)dJ, (void *)dX, (void *)dtoff, (void *)dcost, (void *)dL, (void *)dW}) if (q) (void)hipFree(q);
+    dI = dJ = dtoff = nullptr; dX = dcost = dW = nullptr; dL = nullptr;
 }
 
 // The sweep of profiles/strata_bench.json: the epoch is shortest where a tile holds a handful of nonzeros (fewer blocks leave
@@ -164,9 +138,13 @@ ge_status strata_epoch(Strata *st, const ExactParams &p, int64_t seed, int32_t i
     for (int32_t t = 0; t < P; ++t) {
         const int32_t s = subs[(size_t)t];
         if (!st->sub_used[(size_t)s]) continue;         // all P tiles empty: not launched
-        hipLaunchKernelGGL(k_adagrad_strata, dim3((unsigned)P), dim3(64), sizeof(float) * (size_t)p.D, stream,
-                           p, (const int32_t *)st->dI, (const int32_t *)st->dJ, (const float *)st->dX, (const int32_t *)st->dtoff, st->dcost,
-                           P, s, seed, iteration, shuffle ? 1 : 0);
+        if (st->arith == GE_ARITH_FP32) {
+            strata_fp32_launch(st, p, s, seed, iteration, shuffle, stream);
+        } else {
+            hipLaunchKernelGGL(k_adagrad_strata, dim3((unsigned)P), dim3(64), sizeof(float) * (size_t)p.D, stream,
+                               p, (const int32_t *)st->dI, (const int32_t *)st->dJ, (const float *)st->dX, (const int32_t *)st->dtoff, st->dcost,
+                               P, s, seed, iteration, shuffle ? 1 : 0);
+        }
         ++*launches;
     }
     GE_HIP(hipEventRecord(ev1, stream));

@@ -15,6 +15,7 @@ GE_COST_GLOVE, GE_COST_PGLOVE = 0, 1
 GE_OPT_ADAGRAD, GE_OPT_ADAM, GE_OPT_AMSGRAD = 0, 1, 2
 GE_NORM_NONE, GE_NORM_UNITY, GE_NORM_COUNTS = 0, 1, 2
 GE_MODE_HOGWILD, GE_MODE_DETERMINISTIC, GE_MODE_STRATIFIED = 0, 1, 2
+GE_ARITH_JAVA, GE_ARITH_FP32 = 0, 1
 GE_SHUFFLE_JAVA, GE_SHUFFLE_DEVICE, GE_SHUFFLE_NONE = 0, 1, 2
 GE_HOT_AUTO, GE_HOT_NONE, GE_HOT_ALL = 0, 1, 2
 GE_DTYPE_F32, GE_DTYPE_BF16 = 0, 1
@@ -41,6 +42,7 @@ SYMBOLS = (
     "ge_nn_last_kernel_ms", "ge_nn_destroy",
     "ge_synth_cfg_default", "ge_synth_cfg_size", "ge_synth_coo", "ge_coo_device", "ge_coo_synth_stats", "ge_glove_create_coo",
     "ge_glove_eval_create", "ge_glove_eval_run", "ge_eval_last_kernel_ms", "ge_eval_get", "ge_eval_destroy", "ge_holdout_mask",
+    "ge_glove_set_arith", "ge_glove_get_arith",
 )
 GE_NN_COSINE, GE_NN_DOT = 0, 1
 NN_METRICS = {"cosine": GE_NN_COSINE, "dot": GE_NN_DOT}
@@ -173,6 +175,8 @@ def lib():
     L.ge_glove_rng_state.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.ge_glove_last_kernel_ms.argtypes = [vp, f32p, i32p]
     L.ge_glove_get_info.argtypes = [vp, C.POINTER(GloveInfo)]
+    L.ge_glove_set_arith.argtypes = [vp, C.c_int32]
+    L.ge_glove_get_arith.argtypes = [vp, i32p]
     L.ge_glove_destroy.argtypes = [vp]; L.ge_glove_destroy.restype = None
     L.ge_bca_build.argtypes = [C.POINTER(Csr), C.POINTER(Csr), C.POINTER(BcaCfg), C.POINTER(vp)]
     L.ge_coo_get.argtypes = [vp, i64p, C.POINTER(i32p), C.POINTER(i32p), C.POINTER(f32p), C.POINTER(i64p), f64p]

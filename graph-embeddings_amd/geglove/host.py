@@ -39,6 +39,7 @@ class Configuration:
     Accepts the bean's keys AND the legacy keys present in the shipped YAMLs
     (`bca.reverse`, `bca.predicates`, `similarity[].predicate`), which the Java bean of this
     revision would reject.  New, optional keys live under `device:`:
+      arith: java|fp32 (mode: stratified only; the arithmetic of one update, GE_ARITH_*)
       mode: hogwild|deterministic|stratified   strata: <P, 0 = default>   shuffle: java|device|none   seed: <long>   id: <ordinal>
       hot: auto|none|all   workers: <int>   dtype: f32|bf16
       hot_theta, stale_budget, flush_every, blocks_per_cu (ge_glove_cfg; 0 / absent = library default)
@@ -83,6 +84,7 @@ class Configuration:
             raise InvalidConfigurationException("Invalid BCA parameters, alpha and epsilon are mandatory")
         if not has_out:
             raise InvalidConfigurationException("Invalid output parameters, specify at least one group")
+        device_arith(config.device)
 
     # bean getters used on the hot path
     def getDim(self): return self.dim
@@ -238,6 +240,19 @@ class Optimum:
     def setFinalCost(self, c): self.finalCost = c
 
 
+_ARITH = {"java": capi.GE_ARITH_JAVA, "fp32": capi.GE_ARITH_FP32}
+
+
+def device_arith(dev):
+    """device.arith as a GE_ARITH_* value, checked against device.mode before any device work."""
+    word = str(dev.get("arith", "java")).lower()
+    if word not in _ARITH:
+        raise InvalidConfigurationException("Invalid device.arith, choose one of: java, fp32")
+    if word == "fp32" and str(dev.get("mode", "hogwild")).lower() != "stratified":
+        raise InvalidConfigurationException("device.arith: fp32 needs device.mode: stratified")
+    return _ARITH[word]
+
+
 _MODES = {"hogwild": capi.GE_MODE_HOGWILD, "deterministic": capi.GE_MODE_DETERMINISTIC, "stratified": capi.GE_MODE_STRATIFIED}
 _HOT = {"auto": capi.GE_HOT_AUTO, "none": capi.GE_HOT_NONE, "all": capi.GE_HOT_ALL}
 _SHUFFLES = {"java": capi.GE_SHUFFLE_JAVA, "device": capi.GE_SHUFFLE_DEVICE, "none": capi.GE_SHUFFLE_NONE}
@@ -259,6 +274,7 @@ class Adagrad:
     def __init__(self, coMatrix, config, costFunction, **kw):
         dev = dict(config.device)
         dev.update({k: v for k, v in kw.items() if v is not None})
+        arith = device_arith(dev)
         self.coMatrix, self.config, self.costFunction = coMatrix, config, costFunction
         self.dimension = config.getDim()
         self.vocabSize = coMatrix.vocabSize()
@@ -296,10 +312,16 @@ class Adagrad:
         coo = getattr(coMatrix, "coo", None)
         if coo is not None:                  # a ge_coo handle: a device-resident one is read in place
             capi.check(capi.lib().ge_glove_create_coo(C.byref(cfg), coo.handle, C.byref(self._h)))
-            return
-        I, J, X = coMatrix.I, coMatrix.J, coMatrix.X
-        capi.check(capi.lib().ge_glove_create(C.byref(cfg), _p(I, C.c_int32), _p(J, C.c_int32), _p(X, C.c_float),
-                                              C.byref(self._h)))
+        else:
+            I, J, X = coMatrix.I, coMatrix.J, coMatrix.X
+            capi.check(capi.lib().ge_glove_create(C.byref(cfg), _p(I, C.c_int32), _p(J, C.c_int32), _p(X, C.c_float),
+                                                  C.byref(self._h)))
+        if arith != capi.GE_ARITH_JAVA:
+            try:
+                self.set_arith(arith)
+            except Exception:
+                self.close()
+                raise
 
     # -- IOptimizer -----------------------------------------------------------------------
     def getName(self):
@@ -398,6 +420,15 @@ class Adagrad:
         ms = C.c_float(); n = C.c_int32()
         capi.check(capi.lib().ge_glove_last_kernel_ms(self._h, C.byref(ms), C.byref(n)))
         return ms.value, n.value
+
+    def set_arith(self, arith):
+        """GE_MODE_STRATIFIED handles: the arithmetic of the following epochs, "java" | "fp32" or a GE_ARITH_* value."""
+        capi.check(capi.lib().ge_glove_set_arith(self._h, _ARITH[arith] if isinstance(arith, str) else int(arith)))
+
+    def get_arith(self):
+        a = C.c_int32()
+        capi.check(capi.lib().ge_glove_get_arith(self._h, C.byref(a)))
+        return a.value
 
     def info(self):
         inf = capi.GloveInfo()

@@ -253,6 +253,7 @@ struct Configuration {
     struct { std::string mode = "hogwild", shuffle = "device", hot = "auto", dtype = "f32", save_coo, load_coo;
              long long seed = 0; bool has_seed = false; int id = 0; int workers = 0;
              int strata = 0;        // mode: stratified -- P, 0 = the library's default for the matrix
+             std::string arith = "java";   // mode: stratified -- java | fp32: the arithmetic of one update (GE_ARITH_*)
              // Hogwild tuning (ge_glove_cfg: 0 = library default), layout: list of fixed_cuts | plain_long_rows | separate_tables | packed_records
              double hot_theta = 0, stale_budget = 0; int flush_every = 0, blocks_per_cu = 0, layout_flags = 0;
              long long bca_table_slots = 0, bca_pool_entries = 0;
@@ -354,6 +355,7 @@ struct Configuration {
                     else if (q.first == "id") c.device.id = (int)num(&q.second);
                     else if (q.first == "workers") c.device.workers = (int)num(&q.second);
                     else if (q.first == "strata") c.device.strata = (int)num(&q.second);
+                    else if (q.first == "arith") c.device.arith = q.second.scalar;
                     else if (q.first == "dtype") c.device.dtype = q.second.scalar;
                     else if (q.first == "save_coo") c.device.save_coo = q.second.scalar;      // COO checkpoint
                     else if (q.first == "load_coo") c.device.load_coo = q.second.scalar;
@@ -411,6 +413,8 @@ struct Configuration {
             throw InvalidConfigurationException("device.mode: stratified cannot follow shuffle: java, choose one of: device, none");
         if (c.device.strata < 0 || c.device.strata > 2048) throw InvalidConfigurationException("Invalid device.strata, choose a number from 1 to 2048 (0 = default)");
         if (c.device.strata != 0 && c.device.mode != "stratified") throw InvalidConfigurationException("device.strata needs device.mode: stratified");
+        if (c.device.arith != "java" && c.device.arith != "fp32") throw InvalidConfigurationException("Invalid device.arith, choose one of: java, fp32");
+        if (c.device.arith == "fp32" && c.device.mode != "stratified") throw InvalidConfigurationException("device.arith: fp32 needs device.mode: stratified");
         if (c.device.neighbors < 0 || c.device.neighbors > 128) throw InvalidConfigurationException("Invalid device.neighbors, choose a number from 1 to 128 (0 = off)");
         if (c.device.neighbors_metric != "cosine" && c.device.neighbors_metric != "dot") throw InvalidConfigurationException("Invalid device.neighbors_metric, choose one of: cosine, dot");
         if (!(c.device.holdout >= 0 && c.device.holdout <= 0.5)) throw InvalidConfigurationException("Invalid device.holdout, choose a fraction from 0 to 0.5 (0 = off)");
@@ -455,6 +459,7 @@ struct Configuration {
             for (auto &s : similarity) L.push_back(similarity_to_string(s));
         } else L.push_back("No similarity matching will be performed");
         if (device.mode == "stratified") L.push_back("Stratified trainer: " + (device.strata > 0 ? std::to_string(device.strata) + " strata" : std::string("strata chosen from the matrix")));
+        if (device.arith == "fp32") L.push_back("Stratified arithmetic: fp32");
         if (writingNeighbors()) L.push_back("Nearest neighbours: " + std::to_string(device.neighbors) + " (" + device.neighbors_metric + ")");
         if (holdingOut()) L.push_back("Holdout: " + java_number(device.holdout, false) + (device.holdout_total < 0 ? std::string() :
                                       " (" + std::to_string(device.holdout_held) + " of " + std::to_string(device.holdout_total) + " nonzeros)"));
@@ -1043,13 +1048,17 @@ public:
         if (m.handle()) check(ge_glove_create_coo(&cfg, m.handle(), &h));
         else check(ge_glove_create(&cfg, m.dataI(), m.dataJ(), m.dataX(), &h));
         h_.reset(h);
+        if (config.device.arith == "fp32") check(ge_glove_set_arith(h, GE_ARITH_FP32));
     }
     std::string getName() const override { return name_; }
     std::string scheduleNote() const override {   // stratified handles: P and the epoch's length as a share of the nonzeros
         ge_glove_info info;
         if (ge_glove_get_info(h_.get(), &info) != GE_OK || info.strata == 0) return std::string();
+        int32_t arith = GE_ARITH_JAVA;
+        (void)ge_glove_get_arith(h_.get(), &arith);
         char b[160];
-        std::snprintf(b, sizeof b, "stratified: P = %d, strata_path / N = %.6g", info.strata, coCount_ > 0 ? (double)info.strata_path / (double)coCount_ : 0.0);
+        std::snprintf(b, sizeof b, "stratified: P = %d, strata_path / N = %.6g, arithmetic: %s", info.strata,
+                      coCount_ > 0 ? (double)info.strata_path / (double)coCount_ : 0.0, arith == GE_ARITH_FP32 ? "fp32" : "java");
         return b;
     }
     Optimum optimize() override {                 // Optimizer.optimize, J/opt/Optimizer.java:66-120

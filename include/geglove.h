@@ -87,6 +87,34 @@ enum { GE_NORM_NONE = 0, GE_NORM_UNITY = 1, GE_NORM_COUNTS = 2 };
  *   fields are ignored; row_begin / row_end as for DETERMINISTIC (r and c count this handle's nonzeros). */
 enum { GE_MODE_HOGWILD = 0, GE_MODE_DETERMINISTIC = 1, GE_MODE_STRATIFIED = 2 };
 
+/* The arithmetic of one update of a GE_MODE_STRATIFIED handle (ge_glove_set_arith).  The schedule, the order and every guarantee
+ * of the mode are the same for both: race-free, bytes a function of (input, seed, P) alone, the sequential equivalent that
+ * ge_glove_epoch_order reports.
+ * JAVA (the default): DETERMINISTIC's arithmetic, as stated above.
+ * FP32: for nonzero (i, j, x) of a tile, a = focus[i], b = context[j], D = dim.  Every operation is an IEEE fp32 operation,
+ *   rounded to nearest even, unless marked fp64; nothing is contracted beyond the fmas named here.
+ *   lane shape  the Hogwild one: vw = 4 if D % 4 == 0, else 2 if D % 2 == 0, else 1; nch = ceil(D / (64 * vw)); lane L of 64 holds
+ *               elements [vw * (L + 64 q), + vw) of chunk q < nch.  nch > 4 has no kernel (ge_glove_set_arith: GE_ERR_ARG).
+ *   dot         per lane  part = 0;  for q = 0 .. nch-1, t = 0 .. vw-1:  part = fmaf(a[e], b[e], part)  with e = vw * (L + 64 q) + t
+ *               (an element past the row contributes nothing).  Then the tree: in each row of 16 lanes  v[L] += v[L ^ 1];
+ *               v[L] += v[L ^ 2];  v[L] += v[(L & ~7) | (7 - (L & 7))];  v[L] += v[(L & ~15) | (15 - (L & 15))];  and
+ *               dot = (v[0] + v[16]) + (v[32] + v[48]).
+ *   cost terms  GloVe: l = log((double) x) (fp64), w = x > xmax ? 1 : (float) pow((double) x / xmax, 0.75) (fp64 libm pow);
+ *               pGloVe: l = log((double) (x / (1.0f - x))), w = x: DETERMINISTIC's.  Computed once per nonzero on the first
+ *               switch to FP32 (12 bytes per nonzero).
+ *   ic, wc      ic = (float) ((double) dot + ((double) (fbias[i] + cbias[j]) - l));  wc = w * ic.
+ *   tile cost   cost = (float) ((double) cost + (0.5 * (double) wc) * (double) ic) from 0 per tile; *cost_sum as above.
+ *   AdaGrad     per element, g1 = wc * b, g2 = wc * a from the values read before either row changes:
+ *               a' = a - (g1 / sqrtf(Ga)) * lr,  b' = b - (g2 / sqrtf(Gb)) * lr,  Ga' = Ga + g1 * g1,  Gb' = Gb + g2 * g2;
+ *               fbias' = fbias - wc / sqrtf(Gfb),  Gfb' = Gfb + wc * wc, and the same for cbias: Adagrad.java's expression
+ *               order with every operation in fp32.  sqrtf and / are correctly rounded.
+ *   Adam / AMSGrad  HOGWILD's: m' = fmaf(0.9f, m, (1 - 0.9f) * g);  vn = fmaf(0.999f, v, (1 - 0.999f) * (g * g));
+ *               v' = AMSGrad ? max(v, vn) : vn;  par' = par - corr * m' * (1.0f / (sqrtf(v') + 1e-7f))  (left to right), with
+ *               corr = Adam ? (float) (lr * sqrt(1 - beta2^(t+1)) / (1 - beta1^(t+1))) (fp64, Adam.java:84) : lr;  the context
+ *               row takes g = g2, the focus row g = g1, the biases g = wc.
+ *   Switching between epochs is legal: both arithmetics work on the same plain fp32 tables. */
+enum { GE_ARITH_JAVA = 0, GE_ARITH_FP32 = 1 };
+
 /* Order in which an epoch visits the nonzeros.
  * JAVA:   CoOccurrenceMatrix.shuffle() = cumulative forward Fisher-Yates on one permutation,
  *         drawn from the SAME java.util.Random stream that initialised the parameters
@@ -277,6 +305,12 @@ ge_status ge_glove_rng_state(ge_glove *h, uint64_t *state);
 ge_status ge_glove_last_kernel_ms(ge_glove *h, float *ms, int32_t *launches);
 
 ge_status ge_glove_get_info(ge_glove *h, ge_glove_info *info);
+
+/* GE_MODE_STRATIFIED handles: choose the arithmetic of the following epochs (GE_ARITH_*; JAVA after create).  A NULL handle or an
+ * unknown value is GE_ERR_ARG, a handle of another mode GE_ERR_STATE, GE_ARITH_FP32 with a dim that has no lane shape GE_ERR_ARG.
+ * ge_glove_cfg and ge_glove_info do not carry it. */
+ge_status ge_glove_set_arith(ge_glove *h, int32_t arith);
+ge_status ge_glove_get_arith(const ge_glove *h, int32_t *arith);
 
 void ge_glove_destroy(ge_glove *h);
 

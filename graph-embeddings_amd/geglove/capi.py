@@ -43,6 +43,7 @@ SYMBOLS = (
     "ge_synth_cfg_default", "ge_synth_cfg_size", "ge_synth_coo", "ge_coo_device", "ge_coo_synth_stats", "ge_glove_create_coo",
     "ge_glove_eval_create", "ge_glove_eval_run", "ge_eval_last_kernel_ms", "ge_eval_get", "ge_eval_destroy", "ge_holdout_mask",
     "ge_glove_set_arith", "ge_glove_get_arith",
+    "ge_glove_rank_create", "ge_glove_rank_run", "ge_rank_last_kernel_ms", "ge_rank_last_phase_ms", "ge_rank_summary_size", "ge_rank_destroy",
 )
 GE_NN_COSINE, GE_NN_DOT = 0, 1
 NN_METRICS = {"cosine": GE_NN_COSINE, "dot": GE_NN_DOT}
@@ -121,6 +122,11 @@ class NnCfg(C.Structure):
 class SynthCfg(C.Structure):
     _fields_ = [("vocab_size", C.c_int32), ("row_begin", C.c_int32), ("row_end", C.c_int32), ("nnz", C.c_int64),
                 ("seed", C.c_uint64), ("device", C.c_int32), ("stream", C.c_void_p)]
+
+
+class RankSummary(C.Structure):
+    _fields_ = [("n", C.c_int64), ("mrr", C.c_double), ("mean_rank", C.c_double), ("hits1", C.c_int64), ("hits10", C.c_int64),
+                ("hits100", C.c_int64)]
 
 
 class GeError(RuntimeError):
@@ -234,6 +240,7 @@ def lib():
     _declare_nn(L)
     _declare_synth(L)
     _declare_eval(L)
+    _declare_rank(L)
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int:      # default restype -> ge_status
@@ -595,6 +602,76 @@ def holdout_mask(seed, n, fraction):
     mask = np.empty(n, dtype=np.uint8)
     check(lib().ge_holdout_mask(int(seed) & 0xFFFFFFFFFFFFFFFF, n, float(fraction), mask.ctypes.data_as(C.POINTER(C.c_uint8))))
     return mask
+
+
+def _declare_rank(L):
+    """The ranking section of include/geglove.h."""
+    vp, i32p, i64p, f32p = C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_float)
+    L.ge_rank_summary_size.argtypes = []; L.ge_rank_summary_size.restype = C.c_int32
+    if L.ge_rank_summary_size() != C.sizeof(RankSummary):
+        raise ImportError("libgeglove.so was built from another revision of include/geglove.h (ge_rank_summary is %d bytes there, %d here): "
+                          "rebuild with `make -C graph-embeddings_amd/csrc`" % (L.ge_rank_summary_size(), C.sizeof(RankSummary)))
+    L.ge_glove_rank_create.argtypes = [vp, i32p, i32p, C.c_int64, i64p, i32p, C.POINTER(vp)]
+    L.ge_glove_rank_run.argtypes = [vp, i32p, f32p, C.POINTER(RankSummary)]
+    L.ge_rank_last_kernel_ms.argtypes = [vp, f32p]
+    L.ge_rank_last_phase_ms.argtypes = [vp, f32p, f32p, f32p]
+    L.ge_rank_destroy.argtypes = [vp]; L.ge_rank_destroy.restype = None
+
+
+class Ranking:
+    """A ge_rank set on a trainer handle: Ranking(glove_handle, I, J, filter_ptr, filter_idx), then run() after any epoch.  The
+    filter lists are CSR-shaped (filter_ptr int64[n + 1] into filter_idx, ids of a list strictly ascending); both None = no
+    filter.  Close it before the trainer handle goes."""
+
+    def __init__(self, glove_handle, I, J, filter_ptr=None, filter_idx=None):
+        import numpy as np
+        I = np.ascontiguousarray(I, dtype=np.int32); J = np.ascontiguousarray(J, dtype=np.int32)
+        if not (I.shape == J.shape and I.ndim == 1):
+            raise ValueError("I, J must be one-dimensional arrays of one length")
+        i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        pp = pi = None
+        if filter_ptr is not None:
+            fp = np.ascontiguousarray(filter_ptr, dtype=np.int64)
+            fi = np.ascontiguousarray(filter_idx if filter_idx is not None else [], dtype=np.int32)
+            if fp.shape != (I.shape[0] + 1,) or fi.ndim != 1 or (fp.size and fp[-1] != fi.shape[0]):
+                raise ValueError("filter_ptr must hold n + 1 offsets, the last one the length of filter_idx")
+            pp, pi = fp.ctypes.data_as(i64p), fi.ctypes.data_as(i32p)
+        h = C.c_void_p()
+        check(lib().ge_glove_rank_create(glove_handle, I.ctypes.data_as(i32p), J.ctypes.data_as(i32p), I.shape[0], pp, pi, C.byref(h)))
+        self._h = h
+        self.n = I.shape[0]
+
+    def run(self, rank=True, score=True):
+        """(rank int32[n] or None, score float32[n] or None, summary dict), the arrays in the caller's order."""
+        import numpy as np
+        rk = np.empty(self.n, dtype=np.int32) if rank else None
+        sc = np.empty(self.n, dtype=np.float32) if score else None
+        s = RankSummary()
+        check(lib().ge_glove_rank_run(self._h, rk.ctypes.data_as(C.POINTER(C.c_int32)) if rank else None,
+                                      sc.ctypes.data_as(C.POINTER(C.c_float)) if score else None, C.byref(s)))
+        return rk, sc, {name: getattr(s, name) for name, _ in RankSummary._fields_}
+
+    def kernel_ms(self):
+        ms = C.c_float()
+        check(lib().ge_rank_last_kernel_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    def phase_ms(self):
+        """(staging, target and filter scores, dense count) of the last run, device milliseconds."""
+        a, b, c = C.c_float(), C.c_float(), C.c_float()
+        check(lib().ge_rank_last_phase_ms(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def close(self):
+        if self._h:
+            lib().ge_rank_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def check(status):

@@ -12,6 +12,7 @@
 #pragma once
 
 #include <algorithm>
+#include <cerrno>
 #include <charconv>
 #include <cmath>
 #include <cstdint>
@@ -265,7 +266,10 @@ struct Configuration {
              int neighbors = 0; std::string neighbors_metric = "cosine";
              // F > 0: hold out that share of the nonzeros (ge_holdout_mask), train on the rest, report the held-out mean cost after
              // every epoch and write <name>.holdout.tsv; held / total: the split's counts once the matrix is known (the banner shows them)
-             double holdout = 0; long long holdout_held = -1, holdout_total = -1; } device;
+             double holdout = 0; long long holdout_held = -1, holdout_total = -1;
+             // Q > 0 (needs holdout): after the last epoch rank the first Q held-out nonzeros among all columns, the row's training
+             // nonzeros filtered out (ge_glove_rank_*), and write <name>.rank.tsv; -1 = a value that is no integer >= 0
+             long long rank = 0; } device;
     std::vector<std::string> ignored_keys;     // legacy keys of the shipped YAMLs that the bean does not know
 
     int getThreads() const {       // Configuration.java:71-73
@@ -278,6 +282,7 @@ struct Configuration {
     bool applyingPca() const { return device.pca == "apply"; }
     bool writingNeighbors() const { return device.neighbors > 0; }
     bool holdingOut() const { return device.holdout > 0; }
+    bool ranking() const { return device.rank > 0; }
     // the run's seed: `device.seed`, or the wall clock as Main seeds (Configuration.setThreadLocalRandom(), J/Main.java:62)
     long long runSeed() const { return device.has_seed ? device.seed : (long long)(std::time(nullptr)) * 1000LL; }
     bool usingWeights() const { return has_weights && !weights.empty(); }
@@ -369,6 +374,14 @@ struct Configuration {
                         const double v = std::strtod(t.c_str(), &end);
                         c.device.holdout = (q.second.kind == YNode::Scalar && !t.empty() && *end == 0) ? v : std::numeric_limits<double>::quiet_NaN();
                     }
+                    else if (q.first == "rank") {                                               // an integer >= 0, all of it
+                        const std::string &t = q.second.scalar;
+                        char *end = nullptr;
+                        errno = 0;
+                        const long long v = std::strtoll(t.c_str(), &end, 10);
+                        const bool digits = q.second.kind == YNode::Scalar && !t.empty() && t.find_first_not_of("0123456789") == std::string::npos;
+                        c.device.rank = (digits && *end == 0 && errno == 0 && v < (1LL << 31)) ? v : -1;
+                    }
                     else if (q.first == "exchange") c.device.exchange = q.second.scalar;        // overlap | sync
                     else if (q.first == "transport") c.device.transport = q.second.scalar;      // auto | rccl | host
                     else if (q.first == "wire") c.device.wire = q.second.scalar;                // bf16 | f32
@@ -419,6 +432,8 @@ struct Configuration {
         if (c.device.neighbors_metric != "cosine" && c.device.neighbors_metric != "dot") throw InvalidConfigurationException("Invalid device.neighbors_metric, choose one of: cosine, dot");
         if (!(c.device.holdout >= 0 && c.device.holdout <= 0.5)) throw InvalidConfigurationException("Invalid device.holdout, choose a fraction from 0 to 0.5 (0 = off)");
         if (c.holdingOut() && c.device.gpus > 1) throw InvalidConfigurationException("device.holdout runs on one rank only, set device.gpus: 1");
+        if (c.device.rank < 0) throw InvalidConfigurationException("Invalid device.rank, choose a number of held-out nonzeros to rank (0 = off)");
+        if (c.ranking() && !c.holdingOut()) throw InvalidConfigurationException("device.rank ranks held-out nonzeros, set device.holdout");
     }
 
     static std::string similarity_to_string(const std::map<std::string, std::string> &m) {     // SimilarityGroup.toString
@@ -463,6 +478,7 @@ struct Configuration {
         if (writingNeighbors()) L.push_back("Nearest neighbours: " + std::to_string(device.neighbors) + " (" + device.neighbors_metric + ")");
         if (holdingOut()) L.push_back("Holdout: " + java_number(device.holdout, false) + (device.holdout_total < 0 ? std::string() :
                                       " (" + std::to_string(device.holdout_held) + " of " + std::to_string(device.holdout_total) + " nonzeros)"));
+        if (ranking()) L.push_back("Rank: " + std::to_string(device.rank) + " held-out nonzeros among all columns, training nonzeros filtered");
         return L;
     }
 };
@@ -986,6 +1002,19 @@ public:
     const int32_t *dataJ() const override { return J_.data(); }
     const float *dataX() const override { return X_.data(); }
     int64_t heldCount() const { return (int64_t)hI_.size(); }
+    // `device.rank`: the first min(Q, held) held-out nonzeros in matrix order and, per pair, the kept (training) columns of its row,
+    // ascending and without repeats: the lists of ge_glove_rank_create
+    void rankSet(int64_t Q, std::vector<int32_t> &I, std::vector<int32_t> &J, std::vector<int64_t> &ptr, std::vector<int32_t> &idx) const {
+        const size_t n = (size_t)std::min<int64_t>(Q, heldCount());
+        I.assign(hI_.begin(), hI_.begin() + (std::ptrdiff_t)n); J.assign(hJ_.begin(), hJ_.begin() + (std::ptrdiff_t)n);
+        std::map<int32_t, std::vector<int32_t>> kept;                  // the rows that occur among the pairs
+        for (size_t k = 0; k < n; ++k) kept[I[k]];
+        for (size_t e = 0; e < I_.size(); ++e) { auto it = kept.find(I_[e]); if (it != kept.end()) it->second.push_back(J_[e]); }
+        for (auto &kv : kept) { std::sort(kv.second.begin(), kv.second.end()); kv.second.erase(std::unique(kv.second.begin(), kv.second.end()), kv.second.end()); }
+        ptr.assign(1, 0); idx.clear();
+        for (size_t k = 0; k < n; ++k) { const auto &l = kept[I[k]]; idx.insert(idx.end(), l.begin(), l.end()); ptr.push_back((int64_t)idx.size()); }
+        if (idx.empty()) idx.push_back(0);                             // never a null pointer beside the offsets
+    }
     const int32_t *heldI() const { return hI_.data(); }
     const int32_t *heldJ() const { return hJ_.data(); }
     const float *heldX() const { return hX_.data(); }
@@ -1003,6 +1032,10 @@ struct Optimum {                                 // J/opt/Optimum.java
     std::vector<double> result;
     std::vector<double> costHistory;
     std::vector<double> holdoutHistory;          // `device.holdout`: the held-out mean cost after every epoch (else empty)
+    // `device.rank`: the ranked pairs in matrix order, their ranks and scores, and the summary (n = 0: nothing was ranked)
+    std::vector<int32_t> rankI, rankJ, rank;
+    std::vector<float> rankScore;
+    ge_rank_summary rankSummary{};
 };
 struct IOptimizer {                              // J/opt/IOptimizer.java:6-11
     virtual ~IOptimizer() = default;
@@ -1014,6 +1047,10 @@ struct IOptimizer {                              // J/opt/IOptimizer.java:6-11
     virtual void holdOut(const int32_t *, const int32_t *, const float *, int64_t) { throw std::invalid_argument("this optimizer evaluates no held-out nonzeros"); }
     // the held-out mean cost after the epoch the progress callback is being told about; NaN without a held-out set
     virtual double lastHoldoutCost() const { return std::numeric_limits<double>::quiet_NaN(); }
+    // `device.rank`: rank these pairs among all columns on the trained tables (ge_glove_rank_*), lists as in include/geglove.h
+    virtual void rank(const std::vector<int32_t> &, const std::vector<int32_t> &, const std::vector<int64_t> &, const std::vector<int32_t> &, Optimum &) {
+        throw std::invalid_argument("this optimizer ranks no held-out nonzeros");
+    }
 };
 enum class CostFunction { GLOVE, PGLOVE };       // GloveCost / PGloveCost
 
@@ -1090,6 +1127,16 @@ public:
         eval_.reset(e); nHeld_ = n;
     }
     double lastHoldoutCost() const override { return lastHoldout_; }
+    void rank(const std::vector<int32_t> &I, const std::vector<int32_t> &J, const std::vector<int64_t> &ptr, const std::vector<int32_t> &idx, Optimum &opt) override {
+        if (ge_rank_summary_size() != (int32_t)sizeof(ge_rank_summary))
+            throw std::runtime_error("libgeglove.so and this host were built from different revisions of include/geglove.h; rebuild both");
+        ge_rank *r = nullptr;
+        check(ge_glove_rank_create(h_.get(), I.data(), J.data(), (int64_t)I.size(), ptr.data(), idx.data(), &r));
+        std::unique_ptr<ge_rank, DelRank> set(r);
+        opt.rankI = I; opt.rankJ = J;
+        opt.rank.resize(I.size()); opt.rankScore.resize(I.size());
+        check(ge_glove_rank_run(r, opt.rank.data(), opt.rankScore.data(), &opt.rankSummary));
+    }
     std::vector<double> extractResult() override {
         std::vector<double> out((size_t)vocab_ * (size_t)dim_);
         check(ge_glove_extract_f64(h_.get(), out.data()));
@@ -1098,6 +1145,7 @@ public:
 private:
     struct Del { void operator()(ge_glove *g) const { ge_glove_destroy(g); } };
     struct DelEval { void operator()(ge_eval *e) const { ge_eval_destroy(e); } };
+    struct DelRank { void operator()(ge_rank *r) const { ge_rank_destroy(r); } };
     std::unique_ptr<ge_glove, Del> h_;
     std::unique_ptr<ge_eval, DelEval> eval_;      // declared after h_: destroyed before the handle it reads
     int64_t nHeld_ = 0;
@@ -1377,6 +1425,27 @@ inline std::string writeHoldout(const Configuration &config, const Optimum &opti
         out << b;
     }
     return "wrote " + std::to_string(optimum.holdoutHistory.size()) + " epochs to " + outputFolder + "/" + file;
+}
+
+// `device: { rank: Q }`: <fileName>.rank.tsv carries the banner, then the summary line mrr, mean_rank (%.17g), hits1, hits10, hits100, n,
+// then one line per ranked pair in matrix order: i, j, rank, score (%.9g: text that parses back to the same float).
+inline std::string writeRank(const Configuration &config, const Optimum &optimum, const std::string &fileName, const std::string &outputFolder) {
+    std::filesystem::create_directories(outputFolder);
+    const std::string file = fileName + ".rank.tsv";
+    std::ofstream out(outputFolder + "/" + file);
+    if (!out) throw std::runtime_error("cannot open " + file + " in " + outputFolder);
+    for (auto &l : config.banner()) out << "# " << l << "\n";
+    const ge_rank_summary &s = optimum.rankSummary;
+    char b[200];
+    std::snprintf(b, sizeof b, "%.17g\t%.17g\t%lld\t%lld\t%lld\t%lld\n", s.mrr, s.mean_rank, (long long)s.hits1, (long long)s.hits10, (long long)s.hits100, (long long)s.n);
+    out << b;
+    for (size_t k = 0; k < optimum.rank.size(); ++k) {
+        std::snprintf(b, sizeof b, "%d\t%d\t%d\t%.9g\n", optimum.rankI[k], optimum.rankJ[k], optimum.rank[k], (double)optimum.rankScore[k]);
+        out << b;
+    }
+    std::snprintf(b, sizeof b, "ranked %lld held-out nonzeros: mrr %.6g, mean rank %.6g, hits@1 %lld, hits@10 %lld, hits@100 %lld; wrote ", (long long)s.n, s.mrr, s.mean_rank,
+                  (long long)s.hits1, (long long)s.hits10, (long long)s.hits100);
+    return b + outputFolder + "/" + file;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 // geglove -c <config.yml> : the reference's CLI (J/Main.java:133-160) over the MI355X library.
 // Same single flag, same settings banner, same output files ./out/<name>.{vectors,dict}.tsv
-// (and <name>.neighbors.tsv with `device: { neighbors: K }`, <name>.holdout.tsv with `device: { holdout: F }`).
+// (and <name>.neighbors.tsv with `device: { neighbors: K }`, <name>.holdout.tsv with `device: { holdout: F }`,
+// <name>.rank.tsv with `device: { rank: Q }`).
 #include <ctime>
 #include "ge_host.hpp"
 
@@ -84,6 +85,11 @@ static void runProgram(const Configuration &given) {                        // J
     if (split) { optimizer->holdOut(split->heldI(), split->heldJ(), split->heldX(), split->heldCount()); g_optimizer = optimizer.get(); }
     if (!optimizer->scheduleNote().empty()) log_info("Optimizer", optimizer->scheduleNote());
     Optimum optimum = optimizer->optimize();
+    if (split && config.ranking()) {            // on the tables as the last epoch left them
+        std::vector<int32_t> rI, rJ, fIdx; std::vector<int64_t> fPtr;
+        split->rankSet(config.device.rank, rI, rJ, fPtr, fIdx);
+        optimizer->rank(rI, rJ, fPtr, fIdx, optimum);
+    }
     {
         char b[120];
         std::snprintf(b, sizeof b, "Finished optimization with final cost: %.12g", optimum.finalCost);
@@ -94,6 +100,7 @@ static void runProgram(const Configuration &given) {                        // J
     const long long n = writer.write(optimum, bca, "out");
     log_info("EmbeddingTextWriter", "wrote " + std::to_string(n) + " vectors to out/" + writer.vectorsFile());
     if (split) log_info("Holdout", writeHoldout(config, optimum, outFileName, "out"));
+    if (split && config.ranking()) log_info("Rank", writeRank(config, optimum, outFileName, "out"));
     if (config.writingNeighbors()) {
         std::string warning;
         const std::string done = writeNeighbors(config, optimum, bca, outFileName, "out", warning);

@@ -741,6 +741,48 @@ void      ge_eval_destroy(ge_eval *e);     /* before the ge_glove it was created
  * matrix above).  A function of (seed, k, fraction) alone.  fraction outside (0, 0.5] (NaN included): GE_ERR_ARG. */
 ge_status ge_holdout_mask(uint64_t seed, int64_t n, double fraction, uint8_t *mask);
 
+/* ------------------------------------------------------------------------------------------
+ * Ranking: at which place does column J[k] stand among all V columns when they are ordered by the model's own prediction for
+ * row I[k]?  Its summaries, MRR and hits@k, are the usual measures of a graph embedding.  The reference has no counterpart, so
+ * these are product semantics.  A rank set is n pairs (I[k], J[k]), k = 0 .. n-1, each with an optional filter list F_k (the
+ * known positives of the row, which a "filtered" rank leaves out): filter_ptr[n + 1] (ascending offsets) into filter_idx, the
+ * ids of a list in [0, V) and strictly ascending; filter_ptr == NULL: no filter.
+ *   score      a = focus[I[k]], b = context[c], D = dim:  s(k, c) is the fp32 fmaf chain from 0.0f over ascending d,
+ *              s = fmaf(a[d], b[d], s);  z(k, c) = s(k, c) + cBias[c], one fp32 add.  A NaN z ranks, and is reported, as -inf.
+ *              fBias[i] is the same for every candidate of a query and is not part of z.  Rows are read where the handle
+ *              keeps them, by the rules of ge_glove_eval_*: plain tables, records, packed records, a shard's rebased focus
+ *              rows, bf16 rows widened exactly and the fp32 master row when hub_index[c] >= 0.  A score depends on its two
+ *              rows and the bias only: not on the tile, the batch or the other pairs.
+ *   rank       candidate c precedes j when z(k, c) > z(k, j) as fp32 compares, or z(k, c) == z(k, j) and c < j: the total
+ *              order of ge_nn_* (so -0 = +0).   rank[k] = 1 + #{ c in [0, V), c != J[k], c not in F_k : c precedes J[k] }.
+ *              J[k] inside its own list is ignored.  Ranks are integers and the order is total, so the bytes of a result are
+ *              a function of the input alone; counts are combined by integer atomics, there are no floating-point atomics.
+ *   summary    computed on the host from the ranks: n; mrr = (the fp64 sum of 1.0 / rank[k] in ascending k, from 0.0) / n;
+ *              mean_rank in fp64, the same way; hits1, hits10, hits100 = how many ranks are <= 1, <= 10, <= 100.
+ *   pure read  no trainer table is written; neither the RNG state nor the permutation is touched.
+ * Limits, checked on the host before any device work (GE_ERR_ARG): 1 <= n < 2^31; 1 <= dim <= 1024; I[k] inside the handle's
+ * owned rows [row_begin, row_end); J[k] and every filter id in [0, V); lists strictly ascending; filter_ptr[0] == 0 and
+ * filter_ptr non-decreasing; fewer than 2^35 filter entries in all; no null mandatory argument.  (What needs no handle -- the
+ * null arguments, n, the shape and order of the lists, ids below 0 -- is refused first, so without a device as well.)
+ * Every handle mode is supported.  The set and its lists are uploaded once at creation; ge_glove_rank_run may be called after
+ * any epoch, runs on the trainer handle's stream and is blocking.
+ * Device memory: the tables are NOT read in place.  Every run stages the n query focus rows and the whole context table into
+ * dense fp32 buffers of row length D4 = dim rounded up to 4 (one read and one write of the context table; the tables move
+ * between epochs), so a set holds (V + n) * D4 * 4 bytes + 4 V (biases) + 16 n + 8 per filter entry until ge_rank_destroy.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct ge_rank ge_rank;
+typedef struct { int64_t n; double mrr, mean_rank; int64_t hits1, hits10, hits100; } ge_rank_summary;
+ge_status ge_glove_rank_create(ge_glove *h, const int32_t *I, const int32_t *J, int64_t n,
+                               const int64_t *filter_ptr, const int32_t *filter_idx, ge_rank **out);
+/* out_rank: HOST int32[n] or NULL; out_score: HOST float[n] (z of the target) or NULL; both in the caller's k order.  summary may be NULL. */
+ge_status ge_glove_rank_run(ge_rank *r, int32_t *out_rank, float *out_score, ge_rank_summary *summary);
+/* Device time of the last run's kernels (hipEvents around them; copies not counted), in milliseconds; 0 = none ran. */
+ge_status ge_rank_last_kernel_ms(const ge_rank *r, float *ms);
+/* The same split into staging, the target and filter scores, and the dense count; any out pointer may be NULL. */
+ge_status ge_rank_last_phase_ms(const ge_rank *r, float *stage_ms, float *gather_ms, float *count_ms);
+int32_t   ge_rank_summary_size(void);
+void      ge_rank_destroy(ge_rank *r);     /* before the ge_glove it was created for */
+
 /* ------------------------------------------------------------------------------------------ */
 const char *ge_last_error(void);     /* message of the calling thread's last failed call */
 const char *ge_version(void);

@@ -44,9 +44,14 @@ SYMBOLS = (
     "ge_glove_eval_create", "ge_glove_eval_run", "ge_eval_last_kernel_ms", "ge_eval_get", "ge_eval_destroy", "ge_holdout_mask",
     "ge_glove_set_arith", "ge_glove_get_arith",
     "ge_glove_rank_create", "ge_glove_rank_run", "ge_rank_last_kernel_ms", "ge_rank_last_phase_ms", "ge_rank_summary_size", "ge_rank_destroy",
+    "ge_kmeans_cfg_default", "ge_kmeans_cfg_size", "ge_kmeans_create", "ge_glove_kmeans_create", "ge_kmeans_set_centroids", "ge_kmeans_step",
+    "ge_kmeans_run", "ge_kmeans_get", "ge_kmeans_last_kernel_ms", "ge_kmeans_destroy",
 )
 GE_NN_COSINE, GE_NN_DOT = 0, 1
 NN_METRICS = {"cosine": GE_NN_COSINE, "dot": GE_NN_DOT}
+GE_KM_COSINE, GE_KM_EUCLID = 0, 1
+KM_METRICS = {"cosine": GE_KM_COSINE, "euclid": GE_KM_EUCLID}
+GE_KM_INIT_KEY = 0x4B4D45414E53
 
 
 class GloveCfg(C.Structure):
@@ -117,6 +122,10 @@ class PcaCfg(C.Structure):
 
 class NnCfg(C.Structure):
     _fields_ = [("metric", C.c_int32), ("device", C.c_int32), ("stream", C.c_void_p)]
+
+
+class KmeansCfg(C.Structure):
+    _fields_ = [("metric", C.c_int32), ("k", C.c_int32), ("seed", C.c_uint64), ("device", C.c_int32), ("stream", C.c_void_p)]
 
 
 class SynthCfg(C.Structure):
@@ -241,6 +250,7 @@ def lib():
     _declare_synth(L)
     _declare_eval(L)
     _declare_rank(L)
+    _declare_kmeans(L)
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int:      # default restype -> ge_status
@@ -665,6 +675,131 @@ class Ranking:
     def close(self):
         if self._h:
             lib().ge_rank_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _declare_kmeans(L):
+    """The clustering section of include/geglove.h."""
+    vp, i32p, i64p, f32p, f64p = C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_double)
+    L.ge_kmeans_cfg_default.argtypes = [C.POINTER(KmeansCfg)]; L.ge_kmeans_cfg_default.restype = None
+    L.ge_kmeans_cfg_size.argtypes = []; L.ge_kmeans_cfg_size.restype = C.c_int32
+    if L.ge_kmeans_cfg_size() != C.sizeof(KmeansCfg):
+        raise ImportError("libgeglove.so was built from another revision of include/geglove.h (ge_kmeans_cfg is %d bytes there, %d here): "
+                          "rebuild with `make -C graph-embeddings_amd/csrc`" % (L.ge_kmeans_cfg_size(), C.sizeof(KmeansCfg)))
+    L.ge_kmeans_create.argtypes = [f32p, C.c_int64, C.c_int32, i32p, C.c_int64, C.POINTER(KmeansCfg), C.POINTER(vp)]
+    L.ge_glove_kmeans_create.argtypes = [vp, i32p, C.c_int64, C.POINTER(KmeansCfg), C.POINTER(vp)]
+    L.ge_kmeans_set_centroids.argtypes = [vp, f32p]
+    L.ge_kmeans_step.argtypes = [vp, i64p, f64p]
+    L.ge_kmeans_run.argtypes = [vp, C.c_int32, i32p, i32p]
+    L.ge_kmeans_get.argtypes = [vp, i64p, i32p, i32p, i32p, f32p, f32p, i32p, i32p, i32p, f64p, f64p]
+    L.ge_kmeans_last_kernel_ms.argtypes = [vp, f32p, f32p]
+    L.ge_kmeans_destroy.argtypes = [vp]; L.ge_kmeans_destroy.restype = None
+
+
+class Clustering:
+    """A ge_kmeans handle: Clustering.create(rows, k) / Clustering.create_glove(handle, k), optionally set_centroids(values), then
+    step() -> (changed, objective) or run(max_iter) -> (steps run, converged); labels, best, centroids and sizes read the state."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @staticmethod
+    def _cfg(k, metric, seed, device):
+        cfg = KmeansCfg(); lib().ge_kmeans_cfg_default(C.byref(cfg))
+        cfg.metric, cfg.k, cfg.seed, cfg.device = KM_METRICS.get(metric, metric), k, seed & (2 ** 64 - 1), device
+        return cfg
+
+    @classmethod
+    def create(cls, rows, k, subset=None, metric="cosine", seed=0, device=0):
+        import numpy as np
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        keep, sub, n_sub = Neighbors._subset(subset)
+        h = C.c_void_p()
+        check(lib().ge_kmeans_create(rows.ctypes.data_as(C.POINTER(C.c_float)), rows.shape[0], rows.shape[1], sub, n_sub,
+                                     C.byref(cls._cfg(k, metric, seed, device)), C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def create_glove(cls, glove_handle, k, subset=None, metric="cosine", seed=0):
+        keep, sub, n_sub = Neighbors._subset(subset)
+        h = C.c_void_p()
+        check(lib().ge_glove_kmeans_create(glove_handle, sub, n_sub, C.byref(cls._cfg(k, metric, seed, 0)), C.byref(h)))
+        return cls(h)
+
+    def get(self):
+        """dict: n, dim, k, steps, converged, objective (of the last step), sum_sq"""
+        n, dim, k, steps, conv = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        obj, sq = C.c_double(), C.c_double()
+        check(lib().ge_kmeans_get(self._h, C.byref(n), C.byref(dim), C.byref(k), None, None, None, None, C.byref(steps), C.byref(conv),
+                                  C.byref(obj), C.byref(sq)))
+        return {"n": n.value, "dim": dim.value, "k": k.value, "steps": steps.value, "converged": bool(conv.value),
+                "objective": obj.value, "sum_sq": sq.value}
+
+    def set_centroids(self, centroids):
+        import numpy as np
+        g = self.get()
+        centroids = np.ascontiguousarray(centroids, dtype=np.float32)
+        if centroids.shape != (g["k"], g["dim"]):
+            raise ValueError("centroids must be %d x %d, got %r" % (g["k"], g["dim"], centroids.shape))
+        check(lib().ge_kmeans_set_centroids(self._h, centroids.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def step(self):
+        """One assign and one update: (changed, objective of the assign)."""
+        changed, obj = C.c_int64(), C.c_double()
+        check(lib().ge_kmeans_step(self._h, C.byref(changed), C.byref(obj)))
+        return changed.value, obj.value
+
+    def run(self, max_iter=50):
+        """Steps until no label changes or max_iter steps have run: (steps run, converged)."""
+        steps, conv = C.c_int32(), C.c_int32()
+        check(lib().ge_kmeans_run(self._h, max_iter, C.byref(steps), C.byref(conv)))
+        return steps.value, bool(conv.value)
+
+    def _read(self, slot, shape, dtype, ctype):
+        import numpy as np
+        out = np.empty(shape, dtype=dtype)
+        args = [None] * 11
+        args[slot] = out.ctypes.data_as(C.POINTER(ctype))
+        check(lib().ge_kmeans_get(self._h, *args))
+        return out
+
+    @property
+    def labels(self):
+        import numpy as np
+        return self._read(3, (self.get()["n"],), np.int32, C.c_int32)
+
+    @property
+    def best(self):
+        import numpy as np
+        return self._read(4, (self.get()["n"],), np.float32, C.c_float)
+
+    @property
+    def centroids(self):
+        import numpy as np
+        g = self.get()
+        return self._read(5, (g["k"], g["dim"]), np.float32, C.c_float)
+
+    @property
+    def sizes(self):
+        import numpy as np
+        return self._read(6, (self.get()["k"],), np.int32, C.c_int32)
+
+    @property
+    def kernel_ms(self):
+        """(assign, update) device milliseconds of the last step"""
+        a, u = C.c_float(), C.c_float()
+        check(lib().ge_kmeans_last_kernel_ms(self._h, C.byref(a), C.byref(u)))
+        return a.value, u.value
+
+    def close(self):
+        if self._h:
+            lib().ge_kmeans_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -269,7 +269,10 @@ struct Configuration {
              double holdout = 0; long long holdout_held = -1, holdout_total = -1;
              // Q > 0 (needs holdout): after the last epoch rank the first Q held-out nonzeros among all columns, the row's training
              // nonzeros filtered out (ge_glove_rank_*), and write <name>.rank.tsv; -1 = a value that is no integer >= 0
-             long long rank = 0; } device;
+             long long rank = 0;
+             // K > 0: after the vectors, cluster the kept vertices into K groups (ge_kmeans_*) and write <name>.clusters.tsv;
+             // cosine | euclid; at most `clusters_iterations` Lloyd steps; -1 = a value that is no integer >= 0
+             long long clusters = 0; std::string clusters_metric = "cosine"; long long clusters_iterations = 50; } device;
     std::vector<std::string> ignored_keys;     // legacy keys of the shipped YAMLs that the bean does not know
 
     int getThreads() const {       // Configuration.java:71-73
@@ -283,6 +286,16 @@ struct Configuration {
     bool writingNeighbors() const { return device.neighbors > 0; }
     bool holdingOut() const { return device.holdout > 0; }
     bool ranking() const { return device.rank > 0; }
+    bool clustering() const { return device.clusters > 0; }
+    // the whole scalar as an integer >= 0 below 2^31, else -1
+    static long long whole_number(const YNode &n) {
+        const std::string &t = n.scalar;
+        char *end = nullptr;
+        errno = 0;
+        const long long v = std::strtoll(t.c_str(), &end, 10);
+        const bool digits = n.kind == YNode::Scalar && !t.empty() && t.find_first_not_of("0123456789") == std::string::npos;
+        return (digits && *end == 0 && errno == 0 && v < (1LL << 31)) ? v : -1;
+    }
     // the run's seed: `device.seed`, or the wall clock as Main seeds (Configuration.setThreadLocalRandom(), J/Main.java:62)
     long long runSeed() const { return device.has_seed ? device.seed : (long long)(std::time(nullptr)) * 1000LL; }
     bool usingWeights() const { return has_weights && !weights.empty(); }
@@ -382,6 +395,9 @@ struct Configuration {
                         const bool digits = q.second.kind == YNode::Scalar && !t.empty() && t.find_first_not_of("0123456789") == std::string::npos;
                         c.device.rank = (digits && *end == 0 && errno == 0 && v < (1LL << 31)) ? v : -1;
                     }
+                    else if (q.first == "clusters") c.device.clusters = whole_number(q.second);
+                    else if (q.first == "clusters_metric") c.device.clusters_metric = q.second.scalar;
+                    else if (q.first == "clusters_iterations") c.device.clusters_iterations = whole_number(q.second);
                     else if (q.first == "exchange") c.device.exchange = q.second.scalar;        // overlap | sync
                     else if (q.first == "transport") c.device.transport = q.second.scalar;      // auto | rccl | host
                     else if (q.first == "wire") c.device.wire = q.second.scalar;                // bf16 | f32
@@ -434,6 +450,9 @@ struct Configuration {
         if (c.holdingOut() && c.device.gpus > 1) throw InvalidConfigurationException("device.holdout runs on one rank only, set device.gpus: 1");
         if (c.device.rank < 0) throw InvalidConfigurationException("Invalid device.rank, choose a number of held-out nonzeros to rank (0 = off)");
         if (c.ranking() && !c.holdingOut()) throw InvalidConfigurationException("device.rank ranks held-out nonzeros, set device.holdout");
+        if (c.device.clusters < 0 || c.device.clusters > 65536) throw InvalidConfigurationException("Invalid device.clusters, choose a number from 1 to 65536 (0 = off)");
+        if (c.device.clusters_metric != "cosine" && c.device.clusters_metric != "euclid") throw InvalidConfigurationException("Invalid device.clusters_metric, choose one of: cosine, euclid");
+        if (c.device.clusters_iterations < 1) throw InvalidConfigurationException("Invalid device.clusters_iterations, choose a number from 1 up");
     }
 
     static std::string similarity_to_string(const std::map<std::string, std::string> &m) {     // SimilarityGroup.toString
@@ -479,6 +498,8 @@ struct Configuration {
         if (holdingOut()) L.push_back("Holdout: " + java_number(device.holdout, false) + (device.holdout_total < 0 ? std::string() :
                                       " (" + std::to_string(device.holdout_held) + " of " + std::to_string(device.holdout_total) + " nonzeros)"));
         if (ranking()) L.push_back("Rank: " + std::to_string(device.rank) + " held-out nonzeros among all columns, training nonzeros filtered");
+        if (clustering()) L.push_back("Clusters: " + std::to_string(device.clusters) + " (" + device.clusters_metric + ", at most " +
+                                      std::to_string(device.clusters_iterations) + " iterations)");
         return L;
     }
 };
@@ -1409,6 +1430,67 @@ inline std::string writeNeighbors(const Configuration &config, const Optimum &op
         out.write(line.data(), (std::streamsize)line.size());
     }
     return "wrote " + std::to_string(K) + " " + config.device.neighbors_metric + " neighbours of " + std::to_string(kept) + " vertices to " + outputFolder + "/" + file;
+}
+
+// `device: { clusters: K }`: k-means over the kept vertices (the ones writeNeighbors lists), from the final result (after
+// `device.pca: apply`), on device.id, once -- also after a multi-GPU run -- from the keyed initial sample of the run's seed.
+// <fileName>.clusters.tsv carries the banner, one line `# K<TAB>steps<TAB>converged<TAB>objective` (objective as %.17g), then one
+// line per kept vertex in dict order: its 0-based position in the dict file, its label, its best score in the number format of
+// the vectors file.  `warning` is set when fewer than K vertices are kept and K shrinks; returns the line Main logs.
+inline std::string writeClusters(const Configuration &config, const Optimum &optimum, const CoOccurrenceMatrix &m, const std::string &fileName,
+                                 const std::string &outputFolder, uint64_t seed, std::string &warning) {
+    if (ge_kmeans_cfg_size() != (int32_t)sizeof(ge_kmeans_cfg))
+        throw std::runtime_error("libgeglove.so and this host were built from different revisions of include/geglove.h; rebuild both");
+    const int V = m.vocabSize();
+    if (V < 1 || optimum.result.size() % (size_t)V != 0) throw std::runtime_error("clusters: the result is not a table of V rows");
+    const int D = (int)(optimum.result.size() / (size_t)V);
+    const std::vector<int> keep = keptVertices(config, m);
+    const long long kept = (long long)keep.size();
+    int K = (int)config.device.clusters;
+    if (kept < (long long)K) {
+        K = (int)kept;
+        warning = "only " + std::to_string(kept) + " vertices are written: " + std::to_string(K) + " clusters instead of " +
+                  std::to_string(config.device.clusters);
+    }
+    std::vector<int32_t> label((size_t)kept);
+    std::vector<float> best((size_t)kept);
+    int32_t steps = 0, converged = 0;
+    double objective = 0.0;
+    if (K > 0) {
+        std::vector<float> rows(optimum.result.begin(), optimum.result.end());      // widened fp32 values: exact
+        const std::vector<int32_t> subset(keep.begin(), keep.end());                // ascending by construction
+        ge_kmeans_cfg cfg;
+        ge_kmeans_cfg_default(&cfg);
+        cfg.metric = config.device.clusters_metric == "euclid" ? GE_KM_EUCLID : GE_KM_COSINE;
+        cfg.k = K;
+        cfg.seed = seed;
+        cfg.device = config.device.id;
+        ge_kmeans *raw = nullptr;
+        check(ge_kmeans_create(rows.data(), V, D, subset.data(), (int64_t)subset.size(), &cfg, &raw));
+        struct Del { void operator()(ge_kmeans *p) const { ge_kmeans_destroy(p); } };
+        std::unique_ptr<ge_kmeans, Del> km(raw);
+        check(ge_kmeans_run(km.get(), (int32_t)config.device.clusters_iterations, &steps, &converged));
+        check(ge_kmeans_get(km.get(), nullptr, nullptr, nullptr, label.data(), best.data(), nullptr, nullptr, nullptr, nullptr, &objective, nullptr));
+    }
+    std::filesystem::create_directories(outputFolder);
+    const std::string file = fileName + ".clusters.tsv";
+    std::ofstream out(outputFolder + "/" + file);
+    if (!out) throw std::runtime_error("cannot open " + file + " in " + outputFolder);
+    for (auto &l : config.banner()) out << "# " << l << "\n";
+    char head[120];
+    std::snprintf(head, sizeof head, "# %d\t%d\t%d\t%.17g\n", K, (int)steps, (int)converged, objective);
+    out << head;
+    std::string line;
+    char num[40];
+    for (size_t k = 0; k < keep.size(); ++k) {
+        line = std::to_string(k);
+        line += '\t'; line += std::to_string(label[k]);
+        line += '\t'; line.append(num, (size_t)java_format_11_6E_to((double)best[k], num));
+        line += '\n';
+        out.write(line.data(), (std::streamsize)line.size());
+    }
+    return "wrote " + std::to_string(K) + " " + config.device.clusters_metric + " clusters of " + std::to_string(kept) + " vertices after " +
+           std::to_string(steps) + " iterations (" + (converged ? "converged" : "not converged") + ") to " + outputFolder + "/" + file;
 }
 
 // `device: { holdout: F }`: <fileName>.holdout.tsv carries the banner, then one line per epoch: the iteration as ge_glove_epoch

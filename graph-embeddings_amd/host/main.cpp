@@ -1,7 +1,7 @@
 // geglove -c <config.yml> : the reference's CLI (J/Main.java:133-160) over the MI355X library.
 // Same single flag, same settings banner, same output files ./out/<name>.{vectors,dict}.tsv
 // (and <name>.neighbors.tsv with `device: { neighbors: K }`, <name>.holdout.tsv with `device: { holdout: F }`,
-// <name>.rank.tsv with `device: { rank: Q }`).
+// <name>.rank.tsv with `device: { rank: Q }`, <name>.clusters.tsv with `device: { clusters: K }`).
 #include <ctime>
 #include "ge_host.hpp"
 
@@ -106,6 +106,12 @@ static void runProgram(const Configuration &given) {                        // J
         const std::string done = writeNeighbors(config, optimum, bca, outFileName, "out", warning);
         if (!warning.empty()) log_warn("Neighbors", warning);
         log_info("Neighbors", done);
+    }
+    if (config.clustering()) {
+        std::string warning;
+        const std::string done = writeClusters(config, optimum, bca, outFileName, "out", (uint64_t)config.runSeed(), warning);
+        if (!warning.empty()) log_warn("Clusters", warning);
+        log_info("Clusters", done);
     }
     g_optimizer = nullptr;
 }

@@ -783,6 +783,83 @@ ge_status ge_rank_last_phase_ms(const ge_rank *r, float *stage_ms, float *gather
 int32_t   ge_rank_summary_size(void);
 void      ge_rank_destroy(ge_rank *r);     /* before the ge_glove it was created for */
 
+/* ------------------------------------------------------------------------------------------
+ * Clustering: which vertices belong together?  Lloyd's k-means over a table of vectors, on one device.  The reference stops at
+ * the vectors file and has no counterpart, so these are product semantics:
+ *   indexed rows  as the nearest-neighbour index: host rows with an optional strictly ascending subset, or the vectors of a
+ *                 trainer handle.  Position p = 0 .. n-1 is the p-th indexed row; labels are centroid ids 0 .. K-1 and every
+ *                 per-row result is indexed by position.
+ *   metric        GE_KM_COSINE (spherical k-means): a row is prepared as GE_NN_COSINE prepares it -- n = sqrt(sum_d x_d^2)
+ *                 accumulated in fp64 in ascending d, xh_d = (float)((double)x_d / n), a zero row stays zero.
+ *                 GE_KM_EUCLID: xh = x.
+ *   score         s(p, c) is the fp32 fmaf chain from 0.0f over ascending d, s = fmaf(xh_p[d], cen_c[d], s) (k_km_assign on the
+ *                 fp32 matrix cores, which give exactly that chain);  z(p, c) = s(p, c) + h_c, one fp32 add.  COSINE: h_c = 0.0f.
+ *                 EUCLID: h_c = (float)(-0.5 * q_c), q_c = the fp64 sum from 0.0 over ascending d of the unfused products
+ *                 (double)cen_c[d] * (double)cen_c[d]: argmax_c z = argmin_c |x - cen_c|^2.  A NaN z counts as -inf.
+ *   assign        label[p] = the c that comes first in the total order of the nearest-neighbour results: z descending as fp32
+ *                 compares (so -0 = +0), equal z by ascending c.  best[p] = z(p, label[p]).  A label depends on its row and the
+ *                 centroids only: not on the tile, the batch or the order in which anything arrives.
+ *   update        the members of c are the positions with label == c in ascending p, n_c their number.  S_c[d] is an fp64 sum of
+ *                 (double)xh_p[d] over a fixed partition: pieces of 1024 consecutive members are each summed from 0.0 in
+ *                 ascending member order, then the pieces are summed from 0.0 in ascending order.
+ *                 EUCLID: cen'_c[d] = (float)(S_c[d] / (double)n_c).
+ *                 COSINE: m = sqrt(sum_d S_c[d]^2), fp64, ascending d from 0.0, unfused; cen'_c[d] = (float)(S_c[d] / m).
+ *                 n_c == 0, or m == 0 under COSINE: the centroid keeps its previous value.  No floating-point atomics.
+ *   objective     fp64, over a fixed partition: O_b = the sum of (double)best[p] over p in [1024 b, 1024 (b + 1)) in ascending
+ *                 p, from 0.0; objective = the sum of O_b in ascending b, from 0.0.  Larger is better.  EUCLID: with
+ *                 sum_sq = the same partition sum of r_p, r_p = the fp64 sum over ascending d of the unfused (double)x_p[d]^2
+ *                 taken at creation, the inertia sum_p |x_p - cen_label[p]|^2 is sum_sq - 2 * objective, up to the rounding of z.
+ *   step          one assign with the current centroids, then one update.  *changed = the number of positions whose label
+ *                 differs from the previous assign's (n after the first assign and after ge_kmeans_set_centroids);
+ *                 *objective = that assign's.  ge_kmeans_run repeats steps until changed == 0 or max_iter steps have run.
+ *   initial       a keyed sample without replacement: the K positions with the smallest (SM(seed ^ GE_KM_INIT_KEY, p), p)  (SM: the
+ *   centroids     notation of the synthetic matrix above); centroid t is the prepared row of the t-th smallest: a function of
+ *                 (seed, n, K) alone.  Or K centroids set by value (ge_kmeans_set_centroids): prepared like a query vector of the
+ *                 nearest-neighbour index under COSINE, taken as they are under EUCLID.  There is no k-means++.
+ *   bytes         labels, best scores, centroids, sizes, objective and steps are a function of the input alone, run after run.
+ * Limits, checked on the host before any device work (GE_ERR_ARG without a GPU): 1 <= dim <= 1024; 1 <= k <= min(n, 65536); the
+ * limits of the nearest-neighbour index on rows and subset; a known metric; max_iter >= 1; no null mandatory argument.
+ * Non-finite input rows or centroids: GE_ERR_ARG ("non-finite input").  No device: GE_ERR_HIP.
+ * Device memory: the prepared rows (n * D4 * 4 bytes, D4 = dim rounded up to 4), 20 bytes per row for labels, scores and the
+ * member order, the sort's scratch, and (n / 1024 + k) * D4 * 8 bytes of piece sums, until ge_kmeans_destroy.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct ge_kmeans ge_kmeans;
+enum { GE_KM_COSINE = 0, GE_KM_EUCLID = 1 };
+#define GE_KM_INIT_KEY 0x4B4D45414E53ull     /* "KMEANS" */
+typedef struct {
+    int32_t  metric;         /* GE_KM_COSINE or GE_KM_EUCLID */
+    int32_t  k;              /* number of clusters */
+    uint64_t seed;           /* of the initial sample */
+    int32_t  device;         /* HIP device ordinal */
+    void    *stream;         /* hipStream_t or NULL */
+} ge_kmeans_cfg;
+void      ge_kmeans_cfg_default(ge_kmeans_cfg *cfg);      /* cosine, k 0 (must be set), seed 0, device 0, null stream */
+int32_t   ge_kmeans_cfg_size(void);
+/* rows: HOST float[n_rows * dim], row-major; subset: NULL (every row is indexed; n_subset is ignored) or n_subset strictly
+ * ascending row ids.  The handle holds the initial sample as its centroids and lives on the device until ge_kmeans_destroy. */
+ge_status ge_kmeans_create(const float *rows, int64_t n_rows, int32_t dim, const int32_t *subset, int64_t n_subset,
+                           const ge_kmeans_cfg *cfg, ge_kmeans **out);
+/* The same on the vectors a trainer handle holds -- (focus + context) / 2, what ge_glove_extract_f32 returns -- without the
+ * trip through host memory; bit for bit the handle ge_kmeans_create builds from that output.  Runs on the trainer handle's
+ * device (cfg->device is ignored) and writes no trainer table. */
+ge_status ge_glove_kmeans_create(ge_glove *h, const int32_t *subset, int64_t n_subset, const ge_kmeans_cfg *cfg, ge_kmeans **out);
+/* centroids: HOST float[k * dim].  Starts over: steps = 0, and the next assign reports changed = n. */
+ge_status ge_kmeans_set_centroids(ge_kmeans *p, const float *centroids);
+/* Either out pointer may be NULL. */
+ge_status ge_kmeans_step(ge_kmeans *p, int64_t *changed, double *objective);
+/* *steps_run = the steps this call ran; *converged = 1 when the last of them changed no label.  Either may be NULL. */
+ge_status ge_kmeans_run(ge_kmeans *p, int32_t max_iter, int32_t *steps_run, int32_t *converged);
+/* Any out pointer may be NULL.  labels: HOST int32[n], best: HOST float[n], sizes: HOST int32[k] -- of the last assign, so
+ * GE_ERR_STATE before the first step; centroids: HOST float[k * dim], the current ones (after the last update); *steps = the
+ * steps since creation or ge_kmeans_set_centroids; *converged, *objective: of the last step (0 before the first); *sum_sq: see
+ * "objective" above. */
+ge_status ge_kmeans_get(const ge_kmeans *p, int64_t *n, int32_t *dim, int32_t *k, int32_t *labels, float *best, float *centroids,
+                        int32_t *sizes, int32_t *steps, int32_t *converged, double *objective, double *sum_sq);
+/* Device time of the last step's assign (the objective's block sums included) and update (the member sort included), hipEvents
+ * around the kernels, in milliseconds (0 = none ran); copies are not counted.  Either out pointer may be NULL. */
+ge_status ge_kmeans_last_kernel_ms(const ge_kmeans *p, float *assign_ms, float *update_ms);
+void      ge_kmeans_destroy(ge_kmeans *p);
+
 /* ------------------------------------------------------------------------------------------ */
 const char *ge_last_error(void);     /* message of the calling thread's last failed call */
 const char *ge_version(void);

@@ -9,6 +9,11 @@
 //     so a focus row is resident in ONE worker per epoch.  A row with more than 128 such nonzeros is cut into pieces of
 //     128 that occupy consecutive chunks; the pieces run concurrently, so they publish the row by delta like hub columns
 //     do (cmeta = the row's id) instead of storing it -- no worker ever overwrites another worker's run.
+//   * T part (hub tiles), chunks [0, n_tchunks) IN FRONT of the H part when the handle has them: the densest hub
+//     columns are taken in descending count in GROUPS of tile_g; a tile chunk holds <= 128 nonzeros of one group, whole focus
+//     rows only, rows ascending and inside a row in slot order.  The group's columns stay resident in the worker while each
+//     focus row streams through once.  bA = focus row, bB = slot of the column in its group, cmeta = the group; tcols / tlim hold
+//     every group's column ids (-1: unused slot) and their flush limits.  The H part then holds the other hub columns only.
 // Per position: bA = resident row id (j in H, i in R), bB = streamed row id, L = log term (fp64), W = weight (fp32),
 // border = index of the nonzero in the caller's arrays.
 #pragma once
@@ -33,6 +38,9 @@ struct LayoutRequest {
     int32_t pack_rows;       // 1: rows packed whole into chunks (default); 0: fixed cuts every 128 positions (ablation / tests)
     bool    want_hub_index;  // bf16 rows: dense index of the hub columns
     bool    device_input;    // I, J, X are device arrays (a device-resident ge_coo): read in place, no upload
+    int32_t tile_g;          // hub tiles: columns per group (0: the handle's kernel has no tile walk, never build them)
+    int32_t tile_force;      // 1: every group of >= 2 hub columns becomes tiles (GE_LAYOUT_HUB_TILES); 0: columns with count >= rows / 8
+    int32_t tile_workers;    // sequential workers in flight when the tile kernel runs (`workers` holds when no tile is built)
 };
 
 struct BlockedLayout {
@@ -42,7 +50,12 @@ struct BlockedLayout {
     float   *W = nullptr;
     int32_t *cstart = nullptr;      // n_chunks + 1 positions
     int32_t *cmeta = nullptr;       // n_chunks: H chunk: flush limit of its runs; R chunk: id of the row that publishes by delta, or -1
-    int64_t P = 0, n_chunks = 0, n_hchunks = 0;
+    int32_t *tcols = nullptr;       // hub tiles: n_tgroups x tile_g column ids, -1 for an unused slot
+    int32_t *tlim = nullptr;        // hub tiles: their flush limits
+    int64_t P = 0, n_chunks = 0, n_hchunks = 0;      // n_hchunks: column-major hub chunks, [n_tchunks, n_tchunks + n_hchunks)
+    int64_t n_tchunks = 0, tile_nnz = 0, tile_visits = 0;    // tile chunks, their nonzeros, (focus row, group) pairs with a nonzero
+    int32_t tile_g = 0, tile_cols = 0, n_tgroups = 0;
+    int32_t workers = 0;             // the worker count the hub threshold and the flush limits were computed for
     // what was decided
     int32_t hot_cols = 0; int64_t hot_nnz = 0, hot_threshold = 0;
     int32_t flush_min = LAYOUT_CHUNK;

@@ -53,7 +53,7 @@ struct GloveParams {
     const int32_t *bA, *bB;   // Hogwild, blocked order: resident / streamed row id per re-ordered position
     int64_t n_chunks;         // chunks of <= RUN_CHUNK nonzeros per epoch
     int64_t ticket_end;       // this launch hands out the tickets below this one (n_chunks: the whole epoch; less: one segment of it)
-    int64_t n_hchunks;        // blocked order: the first n_hchunks chunks are hub columns (column-major)
+    int64_t n_hchunks;        // blocked order: the chunks below this one are hub columns (column-major; behind the tile chunks, if any)
     int32_t blocked;          // 1: chunk c = positions [cstart[c], cstart[c+1]) of the re-ordered arrays (ge_layout.h)
     int32_t hot_enabled;      // blocked order: hub chunks publish deltas with atomics
     int32_t flush_every;      // a hub run publishes its delta at least every this many nonzeros (general order)
@@ -72,6 +72,9 @@ struct GloveParams {
     int32_t order_mode;
     uint32_t bij_mask, bij_shift;
     uint32_t bij_key[4];
+    // hub tiles (k_epoch_tiles; behind everything k_adagrad_runs reads, whose argument offsets stay what they were)
+    int64_t n_tchunks;        // blocked order: the first n_tchunks chunks are hub tiles (0 for every other kernel)
+    const int32_t *tcols, *tlim;   // per group and slot: the column id (-1: unused) and its flush limit
 };
 
 // The Hogwild kernel reads (l, w) instead of X: X never changes, so the fp64 log / sqrt run once
@@ -265,15 +268,235 @@ constexpr int wait_vmcnt(int n) { return (n & 15) | ((n >> 4) << 14) | 0x0F70; }
 
 constexpr int RUN_CHUNK = 128;            // nonzeros per worker chunk (2 per lane)
 constexpr int KEY_PAD = 0x7FFFFFFF;       // sorts last; marks the unused tail of the last chunk
+constexpr int TILE_N_AFTER = 4;           // tile_chunk: vector-memory instructions behind a focus pair's request when its image is read
 
+// ---- hub tiles ---------------------------------------------------------------
+// One tile chunk: <= 128 nonzeros of ONE group of G dense hub columns, whole focus rows, rows ascending, slot order inside a row.
+// The G context pairs (row + accumulator row) stay in registers for the chunk, each with a copy as read; every focus pair streams
+// through ONCE -- requested into an LDS image one row ahead, updated in registers by its <= G nonzeros, stored once -- where a
+// column-major hub chunk moves it once per nonzero.  fp32 fat rows of one register chunk only (VW 4, NCH 1: D % 4 == 0, D <= 252).
+// The update is the instruction sequence of epoch_walk's step with A = the context row of the slot and B = the focus row.  The
+// bias of a resident row stays where it was loaded (lane D / 4, component 0: not a row element, so the row arithmetic never
+// touches it) and is read from there by every update -- the G pairs take 16 G registers, the scalars none.
+// A column is published when it has taken its flush limit of updates since it was read, and re-read behind the publish, exactly
+// as a cut hub run; at the end of the chunk every column touched since its last read is published.
+template <int G>
+__device__ __forceinline__ void tile_chunk(const GloveParams &p, const int32_t c_lo, const int32_t c_len, const int32_t grp,
+                                           float *const setA, float *const setB, float *const tr_c, float *const tr_g, double &cost_acc) {
+    static_assert(G >= 2 && G <= 8, "two to eight resident columns");
+    const int lane = threadIdx.x & 63;
+    const int32_t D = p.D, DS = p.DS;
+    const uint32_t row_bytes = (uint32_t)p.RW * 4u;
+    const int bl_lane = (D / 4) & 63;                    // the lane that holds element [D], the bias
+    const bool inr = lane * 4 < D, is_bl = lane == bl_lane;
+    const float lr = p.lr;
+    constexpr int IMG_G = 256;                           // the accumulator row's image behind the row's (epoch_walk: IMG_G)
+    auto rl = [&](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), bl_lane)); };
+
+    // ---- stage: focus row, slot, weight and log term of the chunk's nonzeros into this wave's LDS strip (the chunk is in walk order:
+    // nothing to sort).  The walk reads them back at wave-uniform addresses, so they take no vector register -- and no scalar
+    // load from memory per nonzero either, whose latency a row of two or three nonzeros cannot hide (measured).
+    __shared__ int32_t s_stage[4][5 * RUN_CHUNK];
+    int32_t *const stg = s_stage[threadIdx.x >> 6];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const int e = q * 64 + lane;
+        if (e < c_len) {
+            const int64_t k = (int64_t)c_lo + e;
+            const long long lb = __builtin_bit_cast(long long, p.L[k]);
+            stg[e] = p.bA[k]; stg[RUN_CHUNK + e] = p.bB[k]; stg[2 * RUN_CHUNK + e] = __builtin_bit_cast(int32_t, p.W[k]);
+            stg[3 * RUN_CHUNK + 2 * e] = (int32_t)(lb & 0xFFFFFFFFll); stg[3 * RUN_CHUNK + 2 * e + 1] = (int32_t)(lb >> 32);
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    auto staged = [&](int what, int e) { return rfl(stg[what * RUN_CHUNK + rfl(e)]); };
+    auto row_at = [&](int e) { return staged(0, e); };
+
+    // Requests a focus pair into an image.  `live` false: the same two instructions against zero-sized resources.  Issued once
+    // per row on every path, like the two stores that end a row: the wait below counts them.
+    auto request = [&](float *img, int32_t row, bool live) {
+        const uint32_t rbytes = live ? row_bytes : 0u;
+        load_to_lds<16>(make_rsrc(p.focus + (int64_t)row * DS, rbytes), img, lane * 16);
+        load_to_lds<16>(make_rsrc(p.gsf + (int64_t)row * DS, rbytes), img + IMG_G, lane * 16);
+        asm volatile("" ::: "memory");
+    };
+    int32_t n_row = row_at(0);
+    request(setA, n_row, true);
+
+    // ---- the G resident pairs ----
+    float4 a[G], ga[G], a0[G], ga0[G];
+    int32_t col[G], lim[G], cnt[G];
+    auto ctx_rsrc = [&](int32_t c) { return make_rsrc(p.context + (int64_t)(c < 0 ? 0 : c) * DS, c < 0 ? 0u : row_bytes); };
+    auto gsc_rsrc = [&](int32_t c) { return make_rsrc(p.gsc + (int64_t)(c < 0 ? 0 : c) * DS, c < 0 ? 0u : row_bytes); };
+#pragma unroll
+    for (int s = 0; s < G; ++s) {
+        col[s] = rfl(p.tcols[(int64_t)grp * G + s]); lim[s] = rfl(p.tlim[(int64_t)grp * G + s]); cnt[s] = 0;
+    }
+#pragma unroll
+    for (int s = 0; s < G; ++s) {                        // (an unused slot: zero-sized resources, still two loads)
+        a[s] = buf_load<4, AUX_SC1>(ctx_rsrc(col[s]), lane * 16);
+        ga[s] = buf_load<4, AUX_SC1>(gsc_rsrc(col[s]), lane * 16);
+    }
+#pragma unroll
+    for (int s = 0; s < G; ++s) { a0[s] = a[s]; ga0[s] = ga[s]; }
+
+    // The slot of a nonzero is wave-uniform: a switch over G unrolled bodies, never a register array indexed at run time.  (The
+    // empty asm ends every case so that the compiler cannot merge the cases' tails into one access through a selected pointer --
+    // which is such an index, and put the arrays into scratch.)
+    auto for_slot = [&](const int s, auto &&f) {
+        switch (s) {
+            case 0: f(std::integral_constant<int, 0>{}); asm volatile(""); break;
+            case 1: f(std::integral_constant<int, 1>{}); asm volatile(""); break;
+            case 2: if constexpr (G > 2) f(std::integral_constant<int, 2>{}); asm volatile(""); break;
+            case 3: if constexpr (G > 3) f(std::integral_constant<int, 3>{}); asm volatile(""); break;
+            case 4: if constexpr (G > 4) f(std::integral_constant<int, 4>{}); asm volatile(""); break;
+            case 5: if constexpr (G > 5) f(std::integral_constant<int, 5>{}); asm volatile(""); break;
+            case 6: if constexpr (G > 6) f(std::integral_constant<int, 6>{}); asm volatile(""); break;
+            case 7: if constexpr (G > 7) f(std::integral_constant<int, 7>{}); asm volatile(""); break;
+            default: break;
+        }
+    };
+    // a column's delta through this wave's LDS strip with float atomics, its bias last-writer-wins (epoch_walk: close_run, ATOMIC)
+    auto publish = [&](const int32_t c, const float4 &ca, const float4 &cga, const float4 &ca0, const float4 &cga0) {
+        const __amdgpu_buffer_rsrc_t rs_a = ctx_rsrc(c), rs_ga = gsc_rsrc(c);
+        float4 dc, dg;
+        dc.x = ca.x - ca0.x; dc.y = ca.y - ca0.y; dc.z = ca.z - ca0.z; dc.w = ca.w - ca0.w;
+        dg.x = cga.x - cga0.x; dg.y = cga.y - cga0.y; dg.z = cga.z - cga0.z; dg.w = cga.w - cga0.w;
+        if (is_bl) { dc.x = 0.0f; dg.x = 0.0f; }         // the bias is no part of the delta
+        *reinterpret_cast<float4 *>(tr_c + lane * 4) = dc;
+        *reinterpret_cast<float4 *>(tr_g + lane * 4) = dg;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int e = lane + k * 64;                  // element index; past the row the buffer check drops it
+            __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(tr_c[e], rs_a, e * 4, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(tr_g[e], rs_ga, e * 4, 0, 0);
+        }
+        __builtin_amdgcn_wave_barrier();
+        const float ab = rl(ca.x), gab = rl(cga.x);
+        if (lane == 0) {
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, ab), rs_a, D * 4, 0, AUX_SC1);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, gab), rs_ga, D * 4, 0, AUX_SC1);
+        }
+    };
+
+    float4 b, gb;                                        // the focus pair being updated
+    float bb = 0.0f, gbb = 0.0f;                         // its bias and the bias's accumulator
+    // One nonzero: the pair of its slot is copied out of the resident set, updated by ONE body shared by all slots, and copied
+    // back (eight register moves each way: far less than a body per slot costs in registers and instruction cache).
+    auto update = [&](const int s, const float w, const double l) {
+        float4 ca, cga;
+        // (a slot outside 0 .. G-1 cannot come out of the layout; if it did, the defaults below make the nonzero a no-op on the
+        // resident set -- nothing selected, nothing written back, the publish against zero-sized resources -- not a wild access)
+        int32_t c_cnt = 0, c_lim = 1, c_col = -1;
+        for_slot(s, [&](auto S) { constexpr int q = decltype(S)::value; ca = a[q]; cga = ga[q]; c_cnt = cnt[q]; c_lim = lim[q]; c_col = col[q]; });
+        const float ab = rl(ca.x), gab = rl(cga.x);
+        float part = 0.0f;
+        if (inr) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t) part = __builtin_fmaf(comp<4>(ca, t), comp<4>(b, t), part);
+        }
+        part = wave_sum(part);
+        const float ic = (float)((double)part + ((double)(ab + bb) - l));
+        const float wc = w * ic;
+        cost_acc += (0.5 * (double)wc) * (double)ic;
+        const float wlr = wc * lr;
+        const float nbb = bb - wc * __frsqrt_rn(gbb), ngbb = gbb + wc * wc;
+        if (inr) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const float av = comp<4>(ca, t), bv = comp<4>(b, t);
+                const float grad_b = wc * av, grad_a = wc * bv;
+                const float sa = comp<4>(cga, t), sb = comp<4>(gb, t);
+                comp<4>(b, t)   = __builtin_fmaf(-(wlr * av), __frsqrt_rn(sb), bv);
+                comp<4>(gb, t)  = __builtin_fmaf(grad_b, grad_b, sb);
+                comp<4>(ca, t)  = __builtin_fmaf(-(wlr * bv), __frsqrt_rn(sa), av);
+                comp<4>(cga, t) = __builtin_fmaf(grad_a, grad_a, sa);
+            }
+        }
+        const float w2 = wc * wc;
+        const float nab = ab - wc * __frsqrt_rn(gab), ngab = gab + w2;
+        if (is_bl) { ca.x = nab; cga.x = ngab; }
+        bb = nbb; gbb = ngbb;
+        if (++c_cnt >= c_lim) {                          // a cut: publish, then what memory holds once the publish is in (same wave,
+            float4 ca0, cga0;                            // same addresses: in order)
+            for_slot(s, [&](auto S) { constexpr int q = decltype(S)::value; ca0 = a0[q]; cga0 = ga0[q]; });
+            publish(c_col, ca, cga, ca0, cga0);
+            ca = buf_load<4, AUX_SC1>(ctx_rsrc(c_col), lane * 16);
+            cga = buf_load<4, AUX_SC1>(gsc_rsrc(c_col), lane * 16);
+            for_slot(s, [&](auto S) { constexpr int q = decltype(S)::value; a0[q] = ca; ga0[q] = cga; });
+            c_cnt = 0;
+        }
+        for_slot(s, [&](auto S) { constexpr int q = decltype(S)::value; a[q] = ca; ga[q] = cga; cnt[q] = c_cnt; });
+    };
+
+    // ---- the rows of the chunk ----
+    // One focus row.  CUR (0 / 1) names the image that holds its pair (a compile-time choice, as in epoch_walk's step: the
+    // compiler then knows that the request for the other image does not touch the one read here).
+    int pos = 0;
+    auto walk_row = [&](auto CUR) {
+        const int32_t row = n_row;
+        int nxt = pos + 1;                               // where the row ends, and the row behind it
+        bool more;
+        for (;;) {
+            more = nxt < c_len;
+            n_row = more ? row_at(nxt) : 0;
+            if (!more || n_row != row) break;
+            ++nxt;
+        }
+        const float *const img = decltype(CUR)::value ? setB : setA;
+        request(decltype(CUR)::value ? setA : setB, n_row, more);
+        // Counted by hand (see epoch_walk's step): memory instructions complete in order, and behind this image's request at
+        // least TILE_N_AFTER more have been issued on every path -- the two stores that ended the previous row (before the
+        // first row: the 2 G loads of the resident pairs), then the two loads of the request just above.  Publishes and
+        // re-reads in between only add to them.
+        __builtin_amdgcn_s_waitcnt(wait_vmcnt(TILE_N_AFTER));
+        asm volatile("" ::: "memory");
+        b = *reinterpret_cast<const float4 *>(img + lane * 4);
+        gb = *reinterpret_cast<const float4 *>(img + IMG_G + lane * 4);
+        bb = rl(b.x); gbb = rl(gb.x);
+        for (int e = pos; e < nxt; ++e) {
+            const int s = staged(1, e);
+            const float w = __builtin_bit_cast(float, staged(2, e));
+            const unsigned lo = (unsigned)rfl(stg[3 * RUN_CHUNK + 2 * rfl(e)]), hi = (unsigned)rfl(stg[3 * RUN_CHUNK + 2 * rfl(e) + 1]);
+            const double l = __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+            update(s, w, l);
+        }
+        // the pair goes out once: the row's lanes, the bias lane, zeros in the padding behind it (whole lines, as a streamed row's store)
+        float4 ob = b, ogb = gb;
+        if (!inr) {
+            ob = float4{0.0f, 0.0f, 0.0f, 0.0f}; ogb = ob;
+            if (is_bl) { ob.x = bb; ogb.x = gbb; }
+        }
+        buf_store<4>(ob, make_rsrc(p.focus + (int64_t)row * DS, row_bytes), lane * 16);
+        buf_store<4>(ogb, make_rsrc(p.gsf + (int64_t)row * DS, row_bytes), lane * 16);
+        asm volatile("" ::: "memory");
+        pos = nxt;
+    };
+    while (pos < c_len) {
+        walk_row(std::integral_constant<int, 0>{});
+        if (pos < c_len) walk_row(std::integral_constant<int, 1>{});
+    }
+    // ---- every column touched since it was last read ----
+#pragma nounroll
+    for (int s = 0; s < G; ++s)
+        for_slot(s, [&](auto S) { constexpr int q = decltype(S)::value; if (cnt[q] > 0) publish(col[q], a[q], ga[q], a0[q], ga0[q]); });
+}
+
+// The walk is one inlined body that two kernels instantiate: k_adagrad_runs (TG = 0) and k_epoch_tiles<G> (TG = G), which walks
+// the hub tile chunks [0, n_tchunks) of the layout with tile_chunk above and every other chunk exactly as k_adagrad_runs does.
 // OPT: GE_OPT_ADAGRAD keeps one auxiliary row per side (gradSq), Adam / AMSGrad two (M1, M2).
 // EMB16: the embedding rows (focus, context) are stored as bf16, everything else stays fp32 (BASELINE config C5).
 //   Rows are widened to fp32 when loaded; a resident row stays fp32 in registers for its whole run and is
 //   narrowed once, with STOCHASTIC rounding (an update of 1e-5 on a value of 0.1 is far below half a bf16 ulp and
 //   would always round away).  Hub context rows keep an fp32 master copy (hub32) that their runs read and
 //   publish into with the same atomics as in the fp32 build; they never touch the bf16 table during training.
-template <int VW, int NCH, int OPT, bool EMB16, bool FAT>
-__global__ __launch_bounds__(256, (NCH == 1 && VW == 4 && OPT == GE_OPT_ADAGRAD) ? 5 : 1) void k_adagrad_runs(GloveParams p, int32_t n_workers) {
+template <int VW, int NCH, int OPT, bool EMB16, bool FAT, int TG>
+__device__ __forceinline__ void epoch_walk(const GloveParams &p, const int32_t n_workers) {
     using VT = typename Vec<VW>::T;
     static_assert(!EMB16 || VW == 4, "bf16 embeddings need dim % 4 == 0");
     constexpr bool MOM = OPT != GE_OPT_ADAGRAD;
@@ -375,6 +598,13 @@ __global__ __launch_bounds__(256, (NCH == 1 && VW == 4 && OPT == GE_OPT_ADAGRAD)
             chunk = rfl((int)x);
             res_is_ctx = chunk < p.n_hchunks;
             c_lo = rfl(p.cstart[chunk]); c_len = rfl(p.cstart[chunk + 1]) - c_lo; c_meta = rfl(p.cmeta[chunk]);
+            if constexpr (TG > 0) {
+                static_assert(VW == 4 && NCH == 1 && OPT == GE_OPT_ADAGRAD && !EMB16 && FAT, "hub tiles: fp32 AdaGrad fat rows of one register chunk");
+                if (chunk < p.n_tchunks) {           // a hub tile: c_meta = its group
+                    tile_chunk<TG>(p, c_lo, c_len, c_meta, setA, setB, s_tr[threadIdx.x >> 6][0], s_tr[threadIdx.x >> 6][1], cost_acc);
+                    continue;
+                }
+            }
         }
         // a hub run is cut every flush_lim nonzeros; a long row's piece (c_meta = its id) runs whole
         const int32_t flush_lim = p.blocked ? (res_is_ctx ? c_meta : RUN_CHUNK) : p.flush_every;
@@ -791,6 +1021,21 @@ __global__ __launch_bounds__(256, (NCH == 1 && VW == 4 && OPT == GE_OPT_ADAGRAD)
     if (lane == 0 && cost_acc != 0.0) atomicAdd(p.cost_out, cost_acc);
 }
 
+template <int VW, int NCH, int OPT, bool EMB16, bool FAT>
+__global__ __launch_bounds__(256, (NCH == 1 && VW == 4 && OPT == GE_OPT_ADAGRAD) ? 5 : 1) void k_adagrad_runs(GloveParams p, int32_t n_workers) {
+    epoch_walk<VW, NCH, OPT, EMB16, FAT, 0>(p, n_workers);
+}
+// The epoch of a handle whose layout has hub tiles: three wavefronts per SIMD (at D = 200 the walk runs as fast with three as with
+// five), which leaves 168 registers for the G resident pairs.  G = 4 is the largest group the compiler keeps out of
+// scratch beside the ordinary walk: it takes all 168 registers of three waves per SIMD, with nothing to spare (G = 6 spills 140 bytes
+// per lane, G = 8 324: DESIGN.md 3.1).  A compiler that needs one register more spills; tests/test_hub_tiles_resources.py then fails
+// (no scratch, <= 168) -- the way out is then fewer live values in tile_chunk, or G = 3, not a spill.
+constexpr int TILE_G = 4;                 // columns per hub-tile group: the one instance that is built
+template <int G>
+__global__ __launch_bounds__(256, 3) void k_epoch_tiles(GloveParams p, int32_t n_workers) {
+    epoch_walk<4, 1, GE_OPT_ADAGRAD, false, true, G>(p, n_workers);
+}
+
 // Placement probe: what an epoch does to a record table -- whole records read and written back at random rows, sc1 like the trainer's
 // accesses, one wavefront per stream of rows.  The values are written back unchanged (the table is not yet initialised and nobody
 // else touches it), so the only result is the time.
@@ -871,7 +1116,7 @@ struct ge_glove {
     int hw_workers = 0;
     bool blocked = false;             // Hogwild + DEVICE shuffle: the layout of ge_layout.h
     ge::BlockedLayout lay;            // its device arrays (bA, bB, L, W, border, cstart, cmeta)
-    int64_t n_chunks = 0, n_hchunks = 0;
+    int64_t n_chunks = 0, n_hchunks = 0, n_tchunks = 0;     // n_hchunks: column-major hub chunks, behind the n_tchunks hub tiles
     int flush_every = RUN_CHUNK;
     bool emb16 = false;               // focus/context stored as bf16 (tab[] pointers then address uint16 data)
     bool fat = false;                 // Hogwild: a row is D + 4 floats with its bias at [D] (pick_hogwild); tab[*BIAS] are null
@@ -974,7 +1219,8 @@ void fill_params(const ge_glove *h, GloveParams &p, int32_t iteration) {
     p.cost_kind = h->cfg.cost; p.lr = h->cfg.learning_rate;
     p.order_mode = h->cfg.shuffle == GE_SHUFFLE_JAVA ? ORDER_PERM
                  : h->cfg.shuffle == GE_SHUFFLE_DEVICE ? ORDER_BIJECTION : ORDER_IDENTITY;
-    p.bA = h->lay.bA; p.bB = h->lay.bB; p.cstart = h->lay.cstart; p.cmeta = h->lay.cmeta; p.n_chunks = h->n_chunks; p.n_hchunks = h->n_hchunks;
+    p.bA = h->lay.bA; p.bB = h->lay.bB; p.cstart = h->lay.cstart; p.cmeta = h->lay.cmeta; p.n_chunks = h->n_chunks;
+    p.n_tchunks = h->n_tchunks; p.n_hchunks = h->n_tchunks + h->n_hchunks; p.tcols = h->lay.tcols; p.tlim = h->lay.tlim;
     p.ticket_end = h->n_chunks;
     p.blocked = h->blocked ? 1 : 0; p.hot_enabled = h->cfg.hot_columns != GE_HOT_NONE; p.flush_every = h->flush_every;
     bijection_width(h->blocked ? h->n_chunks : h->cfg.nnz, &p.bij_mask, &p.bij_shift);      // what the keyed bijection permutes
@@ -1138,7 +1384,7 @@ ge_status validate_config(const ge_glove_cfg *cfg, const int32_t *I, const int32
     if (emb16 && (cfg->mode != GE_MODE_HOGWILD || cfg->shuffle != GE_SHUFFLE_DEVICE || cfg->opt != GE_OPT_ADAGRAD || cfg->dim % 4 != 0))
         return ge::fail(GE_ERR_ARG, "bf16 embeddings need mode=hogwild, shuffle=device, opt=adagrad and dim %% 4 == 0 (the reference path is fp32)");
     if (cfg->hot_columns < GE_HOT_AUTO || cfg->hot_columns > GE_HOT_ALL) return ge::fail(GE_ERR_ARG, "invalid hot_columns %d", cfg->hot_columns);
-    if (cfg->hot_theta < 0 || cfg->stale_budget < 0 || cfg->flush_every < 0 || cfg->blocks_per_cu < 0 || (cfg->layout_flags & ~31) != 0)
+    if (cfg->hot_theta < 0 || cfg->stale_budget < 0 || cfg->flush_every < 0 || cfg->blocks_per_cu < 0 || (cfg->layout_flags & ~127) != 0)
         return ge::fail(GE_ERR_ARG, "invalid tuning fields (hot_theta %g, stale_budget %g, flush_every %d, blocks_per_cu %d, layout_flags %d)",
                         (double)cfg->hot_theta, (double)cfg->stale_budget, cfg->flush_every, cfg->blocks_per_cu, cfg->layout_flags);
     int32_t rb = cfg->row_begin, re = cfg->row_end;
@@ -1269,26 +1515,42 @@ ge_status alloc_tables(ge_glove *h) {
 
 // One wavefront = one sequential worker.  Never more workers than N/2048: a small matrix must
 // not degenerate into one giant stale batch (the JVM has at most #cores updates in flight).
-void plan_workers(ge_glove *h) {
+struct WorkerPlan { int blocks_per_cu, blocks, workers; };
+WorkerPlan plan_workers_of(const ge_glove *h, hogwild_fn fn) {
     const ge_glove_cfg &cfg = h->cfg;
     const int64_t N = cfg.nnz;
     const int groups_per_block = 4;
     const int64_t chunks = (N + RUN_CHUNK - 1) / RUN_CHUNK;
     int occ = 0;
-    h->hw_blocks_per_cu = cfg.blocks_per_cu > 0 ? cfg.blocks_per_cu : 4;
-    if (cfg.blocks_per_cu == 0 && hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void *>(h->hw.fn), 256, 0) == hipSuccess && occ > 0)
-        h->hw_blocks_per_cu = occ;                   // every worker resident: one wave of blocks
-    int64_t blocks = std::min<int64_t>((chunks + 3) / 4, (int64_t)h->num_cus * h->hw_blocks_per_cu);
+    WorkerPlan w{};
+    w.blocks_per_cu = cfg.blocks_per_cu > 0 ? cfg.blocks_per_cu : 4;
+    if (cfg.blocks_per_cu == 0 && hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void *>(fn), 256, 0) == hipSuccess && occ > 0)
+        w.blocks_per_cu = occ;                       // every worker resident: one wave of blocks
+    int64_t blocks = std::min<int64_t>((chunks + 3) / 4, (int64_t)h->num_cus * w.blocks_per_cu);
     blocks = std::min<int64_t>(blocks, std::max<int64_t>(1, N / 2048 / groups_per_block));
-    h->hw_blocks = (int)std::max<int64_t>(blocks, 1);
-    h->hw_workers = h->hw_blocks * 4;
+    w.blocks = (int)std::max<int64_t>(blocks, 1);
+    w.workers = w.blocks * 4;
     if (cfg.workers > 0) {                        // explicit worker count (tests, reproducibility)
-        h->hw_workers = (int)std::min<int64_t>(cfg.workers, (int64_t)h->num_cus * 32);
-        h->hw_blocks = (h->hw_workers + 3) / 4;
+        w.workers = (int)std::min<int64_t>(cfg.workers, (int64_t)h->num_cus * 32);
+        w.blocks = (w.workers + 3) / 4;
     } else if (cfg.workers < 0) {                 // fill the device but leave -workers wavefront slots to kernels
-        h->hw_blocks = (int)std::max<int64_t>(1, (int64_t)h->hw_blocks - (-(int64_t)cfg.workers + 3) / 4);   // running beside (collectives)
-        h->hw_workers = h->hw_blocks * 4;
+        w.blocks = (int)std::max<int64_t>(1, (int64_t)w.blocks - (-(int64_t)cfg.workers + 3) / 4);   // running beside (collectives)
+        w.workers = w.blocks * 4;
     }
+    return w;
+}
+void take_plan(ge_glove *h, const WorkerPlan &w) { h->hw_blocks_per_cu = w.blocks_per_cu; h->hw_blocks = w.blocks; h->hw_workers = w.workers; }
+void plan_workers(ge_glove *h) { take_plan(h, plan_workers_of(h, h->hw.fn)); }
+
+// Hub tiles: the kernel with the tile walk exists for one lane shape; a handle of that shape that owns every focus
+// row gets tiles when GE_LAYOUT_HUB_TILES asks for them, or by default from 2^25 nonzeros on (the saving is reasoned and measured at
+// the bench size only; smaller handles keep their chunk table and their kernel).  GE_LAYOUT_NO_HUB_TILES: never.
+bool tiles_possible(const ge_glove *h) {
+    const ge_glove_cfg &cfg = h->cfg;
+    if (cfg.layout_flags & GE_LAYOUT_NO_HUB_TILES) return false;
+    if (h->emb16 || cfg.opt != GE_OPT_ADAGRAD || !h->hw.fat || h->hw.vw != 4 || h->hw.nch != 1) return false;
+    if (cfg.shuffle != GE_SHUFFLE_DEVICE || h->rows != cfg.vocab_size) return false;
+    return (cfg.layout_flags & GE_LAYOUT_HUB_TILES) != 0 || cfg.nnz >= ((int64_t)1 << 25);
 }
 
 // The order a Hogwild epoch visits the nonzeros in.  Device shuffle: the blocked layout of ge_layout.h, built on the device.
@@ -1313,8 +1575,17 @@ ge_status plan_epoch_layout(ge_glove *h, const int32_t *I, const int32_t *J, con
         rq.pack_rows = (cfg.layout_flags & GE_LAYOUT_FIXED_CUTS) ? 0 : 1;
         rq.want_hub_index = h->emb16;
         rq.device_input = device_input;
+        // which columns go into tiles is decided from the counts alone; the workers then come from the kernel that will run,
+        // and the flush limits from the workers (the hub threshold stays that of the ordinary kernel's workers: glove_layout.hip)
+        const hogwild_fn tile_fn = k_epoch_tiles<TILE_G>;
+        WorkerPlan tile_plan{};
+        if (tiles_possible(h)) {
+            tile_plan = plan_workers_of(h, tile_fn);
+            rq.tile_g = TILE_G; rq.tile_force = (cfg.layout_flags & GE_LAYOUT_HUB_TILES) ? 1 : 0; rq.tile_workers = tile_plan.workers;
+        }
         GE_CHECK(ge::build_blocked_layout(rq, I, J, X, h->stream, &h->lay));
-        h->n_chunks = h->lay.n_chunks; h->n_hchunks = h->lay.n_hchunks;
+        if (h->lay.n_tchunks > 0) { h->hw.fn = tile_fn; take_plan(h, tile_plan); }
+        h->n_chunks = h->lay.n_chunks; h->n_hchunks = h->lay.n_hchunks; h->n_tchunks = h->lay.n_tchunks;
         h->hot_cols = h->lay.hot_cols; h->hot_nnz = h->lay.hot_nnz; h->hot_threshold = h->lay.hot_threshold;
         h->flush_every = h->lay.flush_min;
         if (h->emb16) { h->host_hub_index.swap(h->lay.hub_index); h->n_hub = h->lay.n_hub; }
@@ -1678,6 +1949,12 @@ ge_status ge_glove_get_arith(const ge_glove *h, int32_t *arith) {
     return GE_OK;
 }
 
+ge_status ge_glove_tile_info(ge_glove *h, int64_t out[4]) {
+    if (!h || !out) return ge::fail(GE_ERR_ARG, "null argument");
+    out[0] = h->n_tchunks; out[1] = h->lay.tile_nnz; out[2] = h->lay.tile_g; out[3] = h->lay.tile_cols;
+    return GE_OK;
+}
+
 ge_status ge_glove_get_info(ge_glove *h, ge_glove_info *info) {
     if (!h || !info) return ge::fail(GE_ERR_ARG, "null argument");
     std::memset(info, 0, sizeof(*info));
@@ -1696,7 +1973,8 @@ ge_status ge_glove_get_info(ge_glove *h, ge_glove_info *info) {
         const int64_t aux = h->cfg.opt == GE_OPT_ADAGRAD ? 1 : 2;                 // accumulator rows per side
         const int64_t pair = 2 * (emb + aux * acc) + (h->fat ? 0 : 2 * 4 * (1 + aux));   // load + store of a row, its accumulator row(s) and, unless fat, its scalars
         info->runs = h->lay.n_runs;
-        info->schedule_bytes = h->cfg.nnz * (20 + pair) + h->lay.n_runs * pair;
+        // a nonzero streams a pair; inside a hub tile the pair streams once per (focus row, group) instead
+        info->schedule_bytes = h->cfg.nnz * 20 + (h->cfg.nnz - h->lay.tile_nnz + h->lay.tile_visits) * pair + h->lay.n_runs * pair;
     }
     return GE_OK;
 }

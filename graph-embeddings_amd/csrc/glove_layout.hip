@@ -55,38 +55,68 @@ __global__ __launch_bounds__(256) void k_scan_input(const int32_t *I, const int3
     }
 }
 
+// Keys, ascending: tiles [0, tile_keys) = ((group * rows + row) * tile_g + slot), the other hub columns tile_keys + rank, the rest
+// tile_keys + n_hub + row.  tile_slot[j] = group * tile_g + slot of a tile column, else -1 (null: the handle has no tiles);
+// hub_rank[j] ranks the hub columns outside the tiles.  tile_cnt counts the nonzeros of every (group, row).
 __global__ __launch_bounds__(256) void k_sort_keys(const int32_t *I, const int32_t *J, int64_t N, int32_t rb,
-                                                   const int32_t *hub_rank, int32_t n_hub, uint32_t *key, int32_t *val, int32_t *row_cnt) {
+                                                   const int32_t *hub_rank, int32_t n_hub, uint32_t *key, int32_t *val, int32_t *row_cnt,
+                                                   const int32_t *tile_slot, int32_t tile_g, int32_t rows, uint32_t tile_keys, int32_t *tile_cnt) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < N; base += stride) {
         const int64_t k = base + threadIdx.x;
         const bool act = k < N;
         int32_t r = 0; bool rest = false;
         if (act) {
-            const int32_t h = hub_rank[J[k]];
+            const int32_t j = J[k];
+            const int32_t h = hub_rank[j];
+            const int32_t ts = tile_slot ? tile_slot[j] : -1;
             r = I[k] - rb;
-            rest = h < 0;
-            key[k] = rest ? (uint32_t)n_hub + (uint32_t)r : (uint32_t)h;
+            rest = h < 0 && ts < 0;
+            if (ts >= 0) {
+                const int32_t g = ts / tile_g;
+                key[k] = (uint32_t)(((int64_t)g * rows + r) * tile_g + (ts - g * tile_g));
+                atomicAdd(tile_cnt + (int64_t)g * rows + r, 1);
+            } else key[k] = tile_keys + (rest ? (uint32_t)n_hub + (uint32_t)r : (uint32_t)h);
             val[k] = (int32_t)k;
         }
         wave_count(row_cnt, r, rest);
     }
 }
 
+// positions: tiles [0, nT) and the other hub columns [nT, nH) lie where the sort put them; the rest follows its row's place
 __global__ __launch_bounds__(256) void k_place(const int32_t *I, const int32_t *J, const float *X, int64_t N, int32_t rb,
                                                const uint32_t *skey, const int32_t *sval, int32_t n_hub, int64_t nH,
                                                const int32_t *row_src, const int32_t *row_dst, int kind, double xmax,
-                                               int32_t *bA, int32_t *bB, double *L, float *W, int32_t *border) {
+                                               int32_t *bA, int32_t *bB, double *L, float *W, int32_t *border,
+                                               uint32_t tile_keys, int32_t tile_g) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < N; t += stride) {
         const int32_t k = sval[t];
         const int32_t i = I[k], j = J[k];
         int64_t pos; int32_t a, b;
-        if (skey[t] < (uint32_t)n_hub) { pos = t; a = j; b = i; }                 // H: column-major, positions [0, nH)
+        if (skey[t] < tile_keys) { pos = t; a = i; b = (int32_t)(skey[t] % (uint32_t)tile_g); }      // T: resident side = the group, bB = slot
+        else if (skey[t] - tile_keys < (uint32_t)n_hub) { pos = t; a = j; b = i; }                 // H: column-major, positions [nT, nH)
         else { const int32_t r = i - rb; pos = (int64_t)row_dst[r] + (t - nH - row_src[r]); a = i; b = j; }
         double l; float w;
         cost_terms<false>(kind, X[k], xmax, l, w);
         bA[pos] = a; bB[pos] = b; L[pos] = l; W[pos] = w; border[pos] = k;
+    }
+}
+
+// Hub tiles: the cuts of an epoch.  Inside a tile chunk the column in slot s is published and re-read every tlim[s] of its updates,
+// so a chunk with n_s nonzeros in slot s has sum_s n_s / tlim[s] cuts (one lane per chunk; G <= 8).
+__global__ __launch_bounds__(256) void k_tile_cuts(const int32_t *bB, const int32_t *cstart, const int32_t *cmeta, const int32_t *tlim,
+                                                   int64_t n_tchunks, int32_t G, unsigned long long *cuts) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < n_tchunks; c += stride) {
+        const int32_t *lim = tlim + (int64_t)cmeta[c] * G;
+        unsigned long long n = 0;
+        for (int32_t s = 0; s < G; ++s) {
+            int32_t cnt = 0;
+            for (int32_t k = cstart[c]; k < cstart[c + 1]; ++k) cnt += bB[k] == s;
+            n += (unsigned long long)(cnt / lim[s]);
+        }
+        if (n) atomicAdd(cuts, n);
     }
 }
 
@@ -107,8 +137,8 @@ int grid_for(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n 
 namespace ge {
 
 void BlockedLayout::release() {
-    for (void *q : {(void *)bA, (void *)bB, (void *)border, (void *)L, (void *)W, (void *)cstart, (void *)cmeta}) if (q) (void)hipFree(q);
-    bA = bB = border = cstart = cmeta = nullptr; L = nullptr; W = nullptr;
+    for (void *q : {(void *)bA, (void *)bB, (void *)border, (void *)L, (void *)W, (void *)cstart, (void *)cmeta, (void *)tcols, (void *)tlim}) if (q) (void)hipFree(q);
+    bA = bB = border = cstart = cmeta = tcols = tlim = nullptr; L = nullptr; W = nullptr;
 }
 
 ge_status build_blocked_layout(const LayoutRequest &rq, const int32_t *I, const int32_t *J, const float *X,
@@ -183,25 +213,72 @@ ge_status build_blocked_layout(const LayoutRequest &rq, const int32_t *I, const 
         if (shards > 4 && !std::getenv("GE_SYNC_HEAVY_DIV")) div = div * shards / 4;
         heavy_thr = std::max<int64_t>(floor_n, N / div);
     }
-    if (N > 0 && rq.hot_columns != GE_HOT_NONE) {
+    // Hub tiles: which columns go into tiles needs only the counts, and decides which kernel runs and so how many
+    // workers are in flight; the flush limits follow from that number.
+    int32_t workers = std::max(rq.workers, 1);
+    const int32_t G = rq.tile_g;
+    std::vector<int32_t> tile_slot;                // [V] group * G + slot of a tile column, else -1; empty: no tiles
+    std::vector<int32_t> tcols, tlim;              // per group and slot: column (-1: unused), flush limit
+    std::vector<int32_t> hubsR;                    // the hub columns outside the tiles, ascending: the H part
+    int32_t n_tgroups = 0;
+    out->n_tchunks = 0; out->tile_nnz = 0; out->tile_visits = 0; out->tile_g = 0; out->tile_cols = 0; out->n_tgroups = 0;
+    auto hub_threshold = [&](int32_t wk) -> int64_t {
         int64_t thr = rq.hot_columns == GE_HOT_ALL ? 0
-                    : std::max<int64_t>(2, (int64_t)std::ceil(rq.hot_theta * (double)N / (double)std::max(rq.workers, 1)));
+                    : std::max<int64_t>(2, (int64_t)std::ceil(rq.hot_theta * (double)N / (double)std::max(wk, 1)));
         // a shard of a larger run: every column the exchange inside the epoch covers is a hub HERE too, i.e. moved by atomic adds only,
         // so that the other ranks' deltas can be added to it while the epoch kernel runs (the live exchange, sync.hip)
         if (rq.row_end - rq.row_begin < V) thr = std::min(thr, heavy_thr);
+        return thr;
+    };
+    if (N > 0 && rq.hot_columns != GE_HOT_NONE) {
+        if (G >= 2) {
+            const int64_t thr_t = hub_threshold(rq.workers);
+            std::vector<int32_t> el;               // eligible columns, densest first
+            for (int32_t v = 0; v < V; ++v)
+                if (cnt[(size_t)v] >= thr_t && cnt[(size_t)v] > 0 && (rq.tile_force || (int64_t)cnt[(size_t)v] * 8 >= (int64_t)rows)) el.push_back(v);
+            std::stable_sort(el.begin(), el.end(), [&](int32_t a, int32_t b) { return cnt[(size_t)a] > cnt[(size_t)b]; });
+            size_t n_el = el.size();
+            if (n_el % (size_t)G == 1) --n_el;     // a last group of one column stays with the ordinary hub chunks
+            const uint64_t groups = (n_el + (size_t)G - 1) / (size_t)G;
+            // The sort key is 32 bits wide, and the build counts the nonzeros of every (group, row) in a dense table (4 bytes each, on
+            // the device and on the host): bounded under the default gate (columns of density >= 1/8: at most 8 N / rows columns,
+            // so at most 2 N pairs), not under GE_LAYOUT_HUB_TILES.  Too large: no tiles by default, an error where they were asked for.
+            if (groups * (uint64_t)rows * (uint64_t)G + (uint64_t)V + (uint64_t)rows >= ((uint64_t)1 << 32) || groups * (uint64_t)rows > ((uint64_t)1 << 28)) {
+                if (rq.tile_force && n_el >= 2)
+                    return ge::fail(GE_ERR_ARG, "layout hub_tiles: %llu column groups x %d rows are too many for the tile build (forced tiles are for small matrices)",
+                                    (unsigned long long)groups, rows);
+                n_el = 0;
+            }
+            if (n_el >= 2) {
+                n_tgroups = (int32_t)groups;
+                tile_slot.assign((size_t)V, -1); tcols.assign((size_t)n_tgroups * G, -1); tlim.assign((size_t)n_tgroups * G, LAYOUT_CHUNK);
+                for (size_t k = 0; k < n_el; ++k) { tile_slot[(size_t)el[k]] = (int32_t)k; tcols[k] = el[k]; out->tile_nnz += cnt[(size_t)el[k]]; }
+                out->tile_g = G; out->tile_cols = (int32_t)n_el; out->n_tgroups = n_tgroups;
+                workers = std::max(rq.tile_workers, 1);
+            }
+        }
+        // The hub columns are those of the ordinary kernel's worker count whether tiles are built or not: which columns publish
+        // by delta does not depend on how the dense ones among them are walked (and a handle sized after this one's threshold, as
+        // the replay of bench.py --dump-outputs is, stays what it was).  The flush limits below take the workers that will run.
+        const int64_t thr = hub_threshold(rq.workers);
         for (int32_t v = 0; v < V; ++v)
-            if (cnt[(size_t)v] >= thr && cnt[(size_t)v] > 0) { hub_rank[(size_t)v] = (int32_t)hubs.size(); hubs.push_back(v); out->hot_nnz += cnt[(size_t)v]; }
+            if (cnt[(size_t)v] >= thr && cnt[(size_t)v] > 0) {
+                hubs.push_back(v); out->hot_nnz += cnt[(size_t)v];
+                if (tile_slot.empty() || tile_slot[(size_t)v] < 0) { hub_rank[(size_t)v] = (int32_t)hubsR.size(); hubsR.push_back(v); }
+            }
         out->hot_cols = (int32_t)hubs.size();
         out->hot_threshold = thr;
     }
-    const int32_t n_hub = (int32_t)hubs.size();
+    out->workers = workers;
+    const int32_t n_hub = (int32_t)hubsR.size();
+    const uint32_t tile_keys = (uint32_t)((uint64_t)n_tgroups * (uint64_t)rows * (uint64_t)std::max(G, 1));
     // Concurrent runs on one hub column add their deltas; each delta is stale by the length of the run.  Summing K
     // concurrent runs of m updates behaves like one step K*m times too long and diverges once K*m*(lr*w*|row|^2) passes
     // ~1 (measured: K*m = 39k diverges, 10k is stable at the bench scale).  A hub run is therefore cut -- delta
     // published, row re-read -- every m_j updates with K_j * m_j <= stale_budget, K_j = count_j * workers / N.
     auto flush_limit = [&](int32_t col) -> int32_t {
         if (rq.flush_every > 0) return std::min<int32_t>(rq.flush_every, LAYOUT_CHUNK);
-        const double K = std::max(1.0, (double)cnt[(size_t)col] * (double)rq.workers / (double)std::max<int64_t>(N, 1));
+        const double K = std::max(1.0, (double)cnt[(size_t)col] * (double)workers / (double)std::max<int64_t>(N, 1));
         return (int32_t)std::min<double>(LAYOUT_CHUNK, std::max<double>(4.0, std::floor(rq.stale_budget / K)));
     };
     out->flush_min = rq.flush_every > 0 ? std::min<int32_t>(rq.flush_every, LAYOUT_CHUNK) : LAYOUT_CHUNK;
@@ -219,11 +296,33 @@ ge_status build_blocked_layout(const LayoutRequest &rq, const int32_t *I, const 
     GE_HIP(tmp.alloc(&d_val, (size_t)N)); GE_HIP(tmp.alloc(&d_sval, (size_t)N));
     GE_HIP(hipMemcpyAsync(d_rank, hub_rank.data(), sizeof(int32_t) * (size_t)V, hipMemcpyHostToDevice, stream));
     std::vector<int32_t> rcnt((size_t)rows, 0);
+    int32_t *d_tslot = nullptr, *d_tcnt = nullptr;
+    std::vector<int32_t> tcnt;                           // hub tiles: nonzeros of every (group, row)
+    if (n_tgroups > 0) {
+        // The staleness rule K m <= stale_budget with the K of a tile: a worker inside ANY chunk of the group holds all its columns,
+        // so K_g = group nonzeros * workers / N workers hold column j at once (not count_j * workers / N as in a column-major
+        // chunk), each for m of its own updates of j.  One limit per group.
+        for (int32_t g = 0; g < n_tgroups; ++g) {
+            int64_t gn = 0;
+            for (int s = 0; s < G; ++s) if (tcols[(size_t)g * G + s] >= 0) gn += cnt[(size_t)tcols[(size_t)g * G + s]];
+            const double K = std::max(1.0, (double)gn * (double)workers / (double)std::max<int64_t>(N, 1));
+            const int32_t m = rq.flush_every > 0 ? std::min<int32_t>(rq.flush_every, LAYOUT_CHUNK)
+                                                 : (int32_t)std::min<double>(LAYOUT_CHUNK, std::max<double>(4.0, std::floor(rq.stale_budget / K)));
+            for (int s = 0; s < G; ++s) if (tcols[(size_t)g * G + s] >= 0) tlim[(size_t)g * G + s] = m;
+            out->flush_min = std::min(out->flush_min, m);
+        }
+        tcnt.assign((size_t)n_tgroups * (size_t)rows, 0);
+        GE_HIP(tmp.alloc(&d_tslot, (size_t)V)); GE_HIP(tmp.alloc(&d_tcnt, tcnt.size()));
+        GE_HIP(hipMemcpyAsync(d_tslot, tile_slot.data(), sizeof(int32_t) * (size_t)V, hipMemcpyHostToDevice, stream));
+        GE_HIP(hipMemsetAsync(d_tcnt, 0, sizeof(int32_t) * tcnt.size(), stream));
+    }
     if (N > 0) {
-        hipLaunchKernelGGL(k_sort_keys, dim3(grid_for(N)), dim3(256), 0, stream, dI, dJ, N, rb, d_rank, n_hub, d_key, d_val, d_row);
+        hipLaunchKernelGGL(k_sort_keys, dim3(grid_for(N)), dim3(256), 0, stream, dI, dJ, N, rb, d_rank, n_hub, d_key, d_val, d_row,
+                           d_tslot, std::max(G, 1), rows, tile_keys, d_tcnt);
         GE_HIP(hipGetLastError());
+        if (n_tgroups > 0) GE_HIP(hipMemcpyAsync(tcnt.data(), d_tcnt, sizeof(int32_t) * tcnt.size(), hipMemcpyDeviceToHost, stream));
         unsigned bits = 1;
-        while (bits < 32 && ((uint64_t)1 << bits) < (uint64_t)n_hub + (uint64_t)rows) ++bits;
+        while (bits < 32 && ((uint64_t)1 << bits) < (uint64_t)tile_keys + (uint64_t)n_hub + (uint64_t)rows) ++bits;
         size_t tmp_bytes = 0;
         GE_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_key, d_skey, d_val, d_sval, (size_t)N, 0, bits, stream));
         void *d_tmp = nullptr;
@@ -235,19 +334,46 @@ ge_status build_blocked_layout(const LayoutRequest &rq, const int32_t *I, const 
 
     // ---- chunk table ----
     clk.lap("sort");
-    const int64_t nH = out->hot_nnz, nR = N - nH;
+    const int64_t nT = out->tile_nnz, nH = out->hot_nnz, nR = N - nH;      // positions: tiles [0, nT), other hubs [nT, nH), the rest
     std::vector<int32_t> cfill, cmeta;                   // per chunk: positions in it, meta
+    // T: per group the focus rows in ascending order, packed whole; a chunk closes where the next row would overflow it.
+    // Runs: the worker loads every column of the group once per chunk (counted here); a column is published and re-read when
+    // it has taken its limit of updates since it was last read (counted by k_tile_cuts once the chunks are placed).
+    {
+        int64_t placed = 0;
+        for (int32_t g = 0; g < n_tgroups; ++g) {
+            int32_t used = 0;
+            for (int s = 0; s < G; ++s) if (tcols[(size_t)g * G + s] >= 0) ++used;
+            int32_t fill = 0;
+            auto close = [&]() {
+                if (!fill) return;
+                cfill.push_back(fill); cmeta.push_back(g);
+                out->n_runs += used;
+                fill = 0;
+            };
+            const int32_t *tc = tcnt.data() + (size_t)g * (size_t)rows;
+            for (int32_t r = 0; r < rows; ++r) {
+                const int32_t c = tc[r];
+                if (!c) continue;
+                if (fill + c > LAYOUT_CHUNK) close();
+                fill += c; placed += c; ++out->tile_visits;
+            }
+            close();
+        }
+        if (placed != nT) return ge::fail(GE_ERR_STATE, "internal: tile counts cover %lld of %lld nonzeros", (long long)placed, (long long)nT);
+    }
+    out->n_tchunks = (int64_t)cfill.size();
     // H: fixed cuts; a chunk's flush limit is the smallest limit among the columns inside it
     {
-        int64_t pos = 0; size_t hc = 0; int64_t col_end = n_hub ? cnt[(size_t)hubs[0]] : 0;
+        int64_t pos = nT; size_t hc = 0; int64_t col_end = nT + (n_hub ? cnt[(size_t)hubsR[0]] : 0);
         while (pos < nH) {
             const int64_t end = std::min<int64_t>(pos + LAYOUT_CHUNK, nH);
             int32_t m = LAYOUT_CHUNK;
             int64_t q = pos;
             int32_t seg[LAYOUT_CHUNK]; int n_seg = 0;      // nonzeros of each column inside the chunk
             while (q < end) {
-                while (col_end <= q) { ++hc; col_end += cnt[(size_t)hubs[hc]]; }
-                m = std::min(m, flush_limit(hubs[hc]));
+                while (col_end <= q) { ++hc; col_end += cnt[(size_t)hubsR[hc]]; }
+                m = std::min(m, flush_limit(hubsR[hc]));
                 const int64_t q2 = std::min(end, col_end);
                 seg[n_seg++] = (int32_t)(q2 - q);
                 q = q2;
@@ -257,7 +383,7 @@ ge_status build_blocked_layout(const LayoutRequest &rq, const int32_t *I, const 
             pos = end;
         }
     }
-    out->n_hchunks = (int64_t)cfill.size();
+    out->n_hchunks = (int64_t)cfill.size() - out->n_tchunks;
     // R: rows packed whole (best fit over a few open chunks); a long row takes consecutive chunks of its own and leaves
     // its last, partial one open for whole rows behind it
     std::vector<int32_t> row_src((size_t)rows), row_chunk((size_t)rows, -1), row_off((size_t)rows, 0);
@@ -345,10 +471,26 @@ ge_status build_blocked_layout(const LayoutRequest &rq, const int32_t *I, const 
     if (e == hipSuccess && n_chunks) e = hipMemcpyAsync(out->cmeta, cmeta.data(), sizeof(int32_t) * (size_t)n_chunks, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess && N > 0) {
         hipLaunchKernelGGL(k_place, dim3(grid_for(N)), dim3(256), 0, stream, dI, dJ, dX, N, rb, d_skey, d_sval, n_hub, nH, d_src, d_dst,
-                           rq.cost, rq.xmax, out->bA, out->bB, out->L, out->W, out->border);
+                           rq.cost, rq.xmax, out->bA, out->bB, out->L, out->W, out->border, tile_keys, std::max(G, 1));
         e = hipGetLastError();
     }
+    unsigned long long cuts = 0, *d_cuts = nullptr;
+    if (e == hipSuccess && n_tgroups > 0) {
+        e = hipMalloc((void **)&out->tcols, sizeof(int32_t) * tcols.size());
+        if (e == hipSuccess) e = hipMalloc((void **)&out->tlim, sizeof(int32_t) * tlim.size());
+        if (e == hipSuccess) e = tmp.alloc(&d_cuts, 1);
+        if (e == hipSuccess) e = hipMemcpyAsync(out->tcols, tcols.data(), sizeof(int32_t) * tcols.size(), hipMemcpyHostToDevice, stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(out->tlim, tlim.data(), sizeof(int32_t) * tlim.size(), hipMemcpyHostToDevice, stream);
+        if (e == hipSuccess) e = hipMemsetAsync(d_cuts, 0, sizeof(unsigned long long), stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_tile_cuts, dim3(grid_for(out->n_tchunks)), dim3(256), 0, stream, out->bB, out->cstart, out->cmeta, out->tlim,
+                               out->n_tchunks, G, d_cuts);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(&cuts, d_cuts, sizeof(cuts), hipMemcpyDeviceToHost, stream);
+    }
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    out->n_runs += (int64_t)cuts;
     clk.lap("placement kernel");
     if (e != hipSuccess) {
         out->release();

@@ -222,8 +222,19 @@ typedef struct {
  * FIRST_PLACEMENT  take the record tables where the first allocation puts them.  Default: each side's table is allocated up to six
  *                times (the earlier ones held meanwhile), a millisecond of random record reads and write-backs is timed on each, the
  *                fastest is kept and the others freed -- where the driver places a table decides which of two epoch times a handle
- *                gets (same process, same virtual address, 48 or 54 ms) -- ablation / tests. */
-enum { GE_LAYOUT_FIXED_CUTS = 1, GE_LAYOUT_PLAIN_LONG_ROWS = 2, GE_LAYOUT_SEPARATE_TABLES = 4, GE_LAYOUT_PACKED_RECORDS = 8, GE_LAYOUT_FIRST_PLACEMENT = 16 };
+ *                gets (same process, same virtual address, 48 or 54 ms) -- ablation / tests.
+ * HUB_TILES      hub tiles for every group of >= 2 hub columns, whatever the matrix's size and the columns' density -- tests, small
+ *                matrices: the build keeps a counter per (group, focus row) and a 32-bit sort key per (group, row, slot); a matrix
+ *                with more than 2^28 (group, row) pairs, or too many for the key, is refused with GE_ERR_ARG under this flag (by
+ *                default such a handle builds no tiles, and ge_glove_tile_info says so with zeros).
+ *                Hub tiles: the densest hub columns are walked in groups of 4 that stay resident in a worker while
+ *                each focus row streams through once per group instead of once per nonzero.  Default: columns with
+ *                count >= rows / 8, on fp32 AdaGrad handles with dim % 4 == 0, dim <= 252, that own every focus row and hold
+ *                >= 2^25 nonzeros; every other handle keeps its chunk table and its kernel.  Ignored where the handle's kernel
+ *                has no tile walk (bf16 rows, Adam / AMSGrad, other dims, shards).
+ * NO_HUB_TILES   never build hub tiles (wins over HUB_TILES). */
+enum { GE_LAYOUT_FIXED_CUTS = 1, GE_LAYOUT_PLAIN_LONG_ROWS = 2, GE_LAYOUT_SEPARATE_TABLES = 4, GE_LAYOUT_PACKED_RECORDS = 8, GE_LAYOUT_FIRST_PLACEMENT = 16,
+       GE_LAYOUT_HUB_TILES = 32, GE_LAYOUT_NO_HUB_TILES = 64 };
 
 /* What the library decided for a handle (reporting / DESIGN.md numbers). */
 typedef struct {
@@ -305,6 +316,10 @@ ge_status ge_glove_rng_state(ge_glove *h, uint64_t *state);
 ge_status ge_glove_last_kernel_ms(ge_glove *h, float *ms, int32_t *launches);
 
 ge_status ge_glove_get_info(ge_glove *h, ge_glove_info *info);
+
+/* The hub tiles of a handle's layout (GE_LAYOUT_HUB_TILES): out = [tile chunks, nonzeros inside them, columns per group, columns in
+ * tiles]; all zero for a handle without tiles.  ge_glove_info.chunks includes the tile chunks, hub_chunks stays the column-major ones. */
+ge_status ge_glove_tile_info(ge_glove *h, int64_t out[4]);
 
 /* GE_MODE_STRATIFIED handles: choose the arithmetic of the following epochs (GE_ARITH_*; JAVA after create).  A NULL handle or an
  * unknown value is GE_ERR_ARG, a handle of another mode GE_ERR_STATE, GE_ARITH_FP32 with a dim that has no lane shape GE_ERR_ARG.

@@ -47,6 +47,7 @@ SYMBOLS = (
     "ge_glove_rank_create", "ge_glove_rank_run", "ge_rank_last_kernel_ms", "ge_rank_last_phase_ms", "ge_rank_summary_size", "ge_rank_destroy",
     "ge_kmeans_cfg_default", "ge_kmeans_cfg_size", "ge_kmeans_create", "ge_glove_kmeans_create", "ge_kmeans_set_centroids", "ge_kmeans_step",
     "ge_kmeans_run", "ge_kmeans_get", "ge_kmeans_last_kernel_ms", "ge_kmeans_destroy",
+    "ge_glove_predict_create", "ge_glove_predict_run", "ge_predict_last_kernel_ms", "ge_predict_get", "ge_predict_destroy",
 )
 GE_NN_COSINE, GE_NN_DOT = 0, 1
 NN_METRICS = {"cosine": GE_NN_COSINE, "dot": GE_NN_DOT}
@@ -253,6 +254,7 @@ def lib():
     _declare_eval(L)
     _declare_rank(L)
     _declare_kmeans(L)
+    _declare_predict(L)
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int:      # default restype -> ge_status
@@ -677,6 +679,83 @@ class Ranking:
     def close(self):
         if self._h:
             lib().ge_rank_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _declare_predict(L):
+    """The prediction section of include/geglove.h."""
+    vp, i32p, i64p, f32p = C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_float)
+    L.ge_glove_predict_create.argtypes = [vp, i32p, C.c_int64, i64p, i32p, i32p, C.c_int64, C.c_int32, C.POINTER(vp)]
+    L.ge_glove_predict_run.argtypes = [vp, C.c_int32, i32p, f32p, i32p]
+    L.ge_predict_last_kernel_ms.argtypes = [vp, f32p, f32p, f32p]
+    L.ge_predict_get.argtypes = [vp, i64p, i64p, i32p, i32p]
+    L.ge_predict_destroy.argtypes = [vp]; L.ge_predict_destroy.restype = None
+
+
+class Prediction:
+    """A ge_predict set on a trainer handle: Prediction(glove_handle, I, filters, subset, exclude_self), then run(K) after any
+    epoch.  filters: None or (filter_ptr int64[n + 1], filter_idx), CSR-shaped with the ids of a list strictly ascending;
+    subset: None (all columns) or strictly ascending candidate column ids.  Close it before the trainer handle goes."""
+
+    def __init__(self, glove_handle, I, filters=None, subset=None, exclude_self=False):
+        import numpy as np
+        I = np.ascontiguousarray(I, dtype=np.int32)
+        if I.ndim != 1:
+            raise ValueError("I must be a one-dimensional array")
+        i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        pp = pi = ps = None
+        if filters is not None:
+            fp = np.ascontiguousarray(filters[0], dtype=np.int64)
+            fi = np.ascontiguousarray(filters[1] if filters[1] is not None else [], dtype=np.int32)
+            if fp.shape != (I.shape[0] + 1,) or fi.ndim != 1 or (fp.size and fp[-1] != fi.shape[0]):
+                raise ValueError("filter_ptr must hold n + 1 offsets, the last one the length of filter_idx")
+            pp, pi = fp.ctypes.data_as(i64p), fi.ctypes.data_as(i32p)
+        n_sub = 0
+        if subset is not None:
+            sub = np.ascontiguousarray(subset, dtype=np.int32)
+            if sub.ndim != 1:
+                raise ValueError("subset must be a one-dimensional array")
+            ps, n_sub = sub.ctypes.data_as(i32p), sub.shape[0]
+        h = C.c_void_p()
+        check(lib().ge_glove_predict_create(glove_handle, I.ctypes.data_as(i32p), I.shape[0], pp, pi, ps, n_sub, 1 if exclude_self else 0,
+                                            C.byref(h)))
+        self._h = h
+        self.n = I.shape[0]
+
+    def run(self, K):
+        """(index int32[n, K], score float32[n, K], count int32[n]): the K best candidates of every query in order, short lists
+        filled with (-1, -inf)."""
+        import numpy as np
+        K = int(K)
+        shape = (self.n, K if 1 <= K <= 128 else 0)            # a K outside the limits is the library's to refuse
+        index = np.empty(shape, dtype=np.int32)
+        score = np.empty(shape, dtype=np.float32)
+        count = np.empty(self.n, dtype=np.int32)
+        check(lib().ge_glove_predict_run(self._h, K, index.ctypes.data_as(C.POINTER(C.c_int32)), score.ctypes.data_as(C.POINTER(C.c_float)),
+                                         count.ctypes.data_as(C.POINTER(C.c_int32))))
+        return index, score, count
+
+    def kernel_ms(self):
+        """(staging, score and select, merge) of the last run, device milliseconds."""
+        a, b, c = C.c_float(), C.c_float(), C.c_float()
+        check(lib().ge_predict_last_kernel_ms(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def info(self):
+        """{n, candidates, dim, ranges}: ranges = the candidate ranges of the last run's grid (0 before the first run)."""
+        n, m, d, r = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int32()
+        check(lib().ge_predict_get(self._h, C.byref(n), C.byref(m), C.byref(d), C.byref(r)))
+        return {"n": n.value, "candidates": m.value, "dim": d.value, "ranges": r.value}
+
+    def close(self):
+        if self._h:
+            lib().ge_predict_destroy(self._h)
             self._h = None
 
     def __del__(self):

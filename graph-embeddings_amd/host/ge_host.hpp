@@ -272,7 +272,10 @@ struct Configuration {
              long long rank = 0;
              // K > 0: after the vectors, cluster the kept vertices into K groups (ge_kmeans_*) and write <name>.clusters.tsv;
              // cosine | euclid; at most `clusters_iterations` Lloyd steps; -1 = a value that is no integer >= 0
-             long long clusters = 0; std::string clusters_metric = "cosine"; long long clusters_iterations = 50; } device;
+             long long clusters = 0; std::string clusters_metric = "cosine"; long long clusters_iterations = 50;
+             // K > 0: after the last epoch list the K best missing links of every kept vertex among the kept vertices, the row's known
+             // nonzeros and the vertex itself left out (ge_glove_predict_*), and write <name>.links.tsv; -1 = a value that is no integer >= 0
+             long long predict = 0; } device;
     std::vector<std::string> ignored_keys;     // legacy keys of the shipped YAMLs that the bean does not know
 
     int getThreads() const {       // Configuration.java:71-73
@@ -287,6 +290,7 @@ struct Configuration {
     bool holdingOut() const { return device.holdout > 0; }
     bool ranking() const { return device.rank > 0; }
     bool clustering() const { return device.clusters > 0; }
+    bool predicting() const { return device.predict > 0; }
     // the whole scalar as an integer >= 0 below 2^31, else -1
     static long long whole_number(const YNode &n) {
         const std::string &t = n.scalar;
@@ -398,6 +402,7 @@ struct Configuration {
                     else if (q.first == "clusters") c.device.clusters = whole_number(q.second);
                     else if (q.first == "clusters_metric") c.device.clusters_metric = q.second.scalar;
                     else if (q.first == "clusters_iterations") c.device.clusters_iterations = whole_number(q.second);
+                    else if (q.first == "predict") c.device.predict = whole_number(q.second);
                     else if (q.first == "exchange") c.device.exchange = q.second.scalar;        // overlap | sync
                     else if (q.first == "transport") c.device.transport = q.second.scalar;      // auto | rccl | host
                     else if (q.first == "wire") c.device.wire = q.second.scalar;                // bf16 | f32
@@ -455,6 +460,9 @@ struct Configuration {
         if (c.device.clusters < 0 || c.device.clusters > 65536) throw InvalidConfigurationException("Invalid device.clusters, choose a number from 1 to 65536 (0 = off)");
         if (c.device.clusters_metric != "cosine" && c.device.clusters_metric != "euclid") throw InvalidConfigurationException("Invalid device.clusters_metric, choose one of: cosine, euclid");
         if (c.device.clusters_iterations < 1) throw InvalidConfigurationException("Invalid device.clusters_iterations, choose a number from 1 up");
+        if (c.device.predict < 0 || c.device.predict > 128)
+            throw InvalidConfigurationException("Invalid device.predict, choose a number of links to predict per vertex from 1 to 128 (0 = off)");
+        if (c.predicting() && c.device.gpus > 1) throw InvalidConfigurationException("device.predict runs on one rank only, set device.gpus: 1");
     }
 
     static std::string similarity_to_string(const std::map<std::string, std::string> &m) {     // SimilarityGroup.toString
@@ -502,6 +510,7 @@ struct Configuration {
         if (ranking()) L.push_back("Rank: " + std::to_string(device.rank) + " held-out nonzeros among all columns, training nonzeros filtered");
         if (clustering()) L.push_back("Clusters: " + std::to_string(device.clusters) + " (" + device.clusters_metric + ", at most " +
                                       std::to_string(device.clusters_iterations) + " iterations)");
+        if (predicting()) L.push_back("Predict: the " + std::to_string(device.predict) + " best missing links of every kept vertex, known nonzeros filtered");
         return L;
     }
 };
@@ -1059,6 +1068,11 @@ struct Optimum {                                 // J/opt/Optimum.java
     std::vector<int32_t> rankI, rankJ, rank;
     std::vector<float> rankScore;
     ge_rank_summary rankSummary{};
+    // `device.predict`: the query vertices in dict order and, per vertex, K slots of (column, score) of which the first
+    // predictCount hold predictions (K = 0: nothing was predicted)
+    int32_t predictK = 0;
+    std::vector<int32_t> predictRows, predictIndex, predictCount;
+    std::vector<float> predictScore;
 };
 struct IOptimizer {                              // J/opt/IOptimizer.java:6-11
     virtual ~IOptimizer() = default;
@@ -1073,6 +1087,11 @@ struct IOptimizer {                              // J/opt/IOptimizer.java:6-11
     // `device.rank`: rank these pairs among all columns on the trained tables (ge_glove_rank_*), lists as in include/geglove.h
     virtual void rank(const std::vector<int32_t> &, const std::vector<int32_t> &, const std::vector<int64_t> &, const std::vector<int32_t> &, Optimum &) {
         throw std::invalid_argument("this optimizer ranks no held-out nonzeros");
+    }
+    // `device.predict`: the K best candidates of every row of I among `subset` on the trained tables (ge_glove_predict_*), the row
+    // itself left out, lists as in include/geglove.h
+    virtual void predict(const std::vector<int32_t> &, const std::vector<int64_t> &, const std::vector<int32_t> &, const std::vector<int32_t> &, int32_t, Optimum &) {
+        throw std::invalid_argument("this optimizer predicts no links");
     }
 };
 enum class CostFunction { GLOVE, PGLOVE };       // GloveCost / PGloveCost
@@ -1160,6 +1179,15 @@ public:
         opt.rank.resize(I.size()); opt.rankScore.resize(I.size());
         check(ge_glove_rank_run(r, opt.rank.data(), opt.rankScore.data(), &opt.rankSummary));
     }
+    void predict(const std::vector<int32_t> &I, const std::vector<int64_t> &ptr, const std::vector<int32_t> &idx, const std::vector<int32_t> &subset, int32_t K,
+                 Optimum &opt) override {
+        ge_predict *p = nullptr;
+        check(ge_glove_predict_create(h_.get(), I.data(), (int64_t)I.size(), ptr.data(), idx.data(), subset.data(), (int64_t)subset.size(), 1, &p));
+        std::unique_ptr<ge_predict, DelPredict> set(p);
+        opt.predictK = K; opt.predictRows = I;
+        opt.predictIndex.resize(I.size() * (size_t)K); opt.predictScore.resize(I.size() * (size_t)K); opt.predictCount.resize(I.size());
+        check(ge_glove_predict_run(p, K, opt.predictIndex.data(), opt.predictScore.data(), opt.predictCount.data()));
+    }
     std::vector<double> extractResult() override {
         std::vector<double> out((size_t)vocab_ * (size_t)dim_);
         check(ge_glove_extract_f64(h_.get(), out.data()));
@@ -1169,6 +1197,7 @@ private:
     struct Del { void operator()(ge_glove *g) const { ge_glove_destroy(g); } };
     struct DelEval { void operator()(ge_eval *e) const { ge_eval_destroy(e); } };
     struct DelRank { void operator()(ge_rank *r) const { ge_rank_destroy(r); } };
+    struct DelPredict { void operator()(ge_predict *p) const { ge_predict_destroy(p); } };
     std::unique_ptr<ge_glove, Del> h_;
     std::unique_ptr<ge_eval, DelEval> eval_;      // declared after h_: destroyed before the handle it reads
     int64_t nHeld_ = 0;
@@ -1530,6 +1559,54 @@ inline std::string writeRank(const Configuration &config, const Optimum &optimum
     std::snprintf(b, sizeof b, "ranked %lld held-out nonzeros: mrr %.6g, mean rank %.6g, hits@1 %lld, hits@10 %lld, hits@100 %lld; wrote ", (long long)s.n, s.mrr, s.mean_rank,
                   (long long)s.hits1, (long long)s.hits10, (long long)s.hits100);
     return b + outputFolder + "/" + file;
+}
+
+// `device: { predict: K }`: the set of ge_glove_predict_create -- the kept vertices in dict order as queries and as the candidate
+// subset, and per query the columns of its row among the nonzeros of `m` (the matrix the trainer saw: under `device.holdout` the
+// kept ones), ascending and without repeats.  Empty when no vertex is kept.
+inline void predictSet(const Configuration &config, const CoOccurrenceMatrix &m, std::vector<int32_t> &I, std::vector<int64_t> &ptr, std::vector<int32_t> &idx) {
+    const std::vector<int> keep = keptVertices(config, m);
+    I.assign(keep.begin(), keep.end());                                             // ascending by construction
+    std::vector<int32_t> slot((size_t)m.vocabSize(), -1);                           // vertex id -> its query
+    for (size_t k = 0; k < keep.size(); ++k) slot[(size_t)keep[k]] = (int32_t)k;
+    std::vector<std::vector<int32_t>> lists(keep.size());
+    const int32_t *mi = m.dataI(), *mj = m.dataJ();
+    const int64_t N = m.coOccurrenceCount();
+    for (int64_t e = 0; e < N; ++e) { const int32_t k = slot[(size_t)mi[e]]; if (k >= 0) lists[(size_t)k].push_back(mj[e]); }
+    ptr.assign(1, 0); idx.clear();
+    for (auto &l : lists) {
+        std::sort(l.begin(), l.end()); l.erase(std::unique(l.begin(), l.end()), l.end());
+        idx.insert(idx.end(), l.begin(), l.end()); ptr.push_back((int64_t)idx.size());
+    }
+    if (idx.empty()) idx.push_back(0);                                              // never a null pointer beside the offsets
+}
+
+// <fileName>.links.tsv carries the banner, then one line per kept vertex in dict order: its 0-based position in the dict file, then
+// `count` pairs position<TAB>score, best first, scores as %.9g (text that parses back to the same float).
+inline std::string writeLinks(const Configuration &config, const Optimum &optimum, const CoOccurrenceMatrix &m, const std::string &fileName,
+                              const std::string &outputFolder) {
+    const size_t K = (size_t)optimum.predictK, kept = optimum.predictRows.size();
+    std::vector<int32_t> position((size_t)m.vocabSize(), -1);                       // vertex id -> line of the dict file
+    for (size_t k = 0; k < kept; ++k) position[(size_t)optimum.predictRows[k]] = (int32_t)k;
+    std::filesystem::create_directories(outputFolder);
+    const std::string file = fileName + ".links.tsv";
+    std::ofstream out(outputFolder + "/" + file);
+    if (!out) throw std::runtime_error("cannot open " + file + " in " + outputFolder);
+    for (auto &l : config.banner()) out << "# " << l << "\n";
+    std::string line;
+    char num[40];
+    long long listed = 0;
+    for (size_t k = 0; k < kept; ++k) {
+        line = std::to_string(k);
+        for (size_t t = 0; t < (size_t)optimum.predictCount[k]; ++t) {
+            std::snprintf(num, sizeof num, "\t%d\t%.9g", position[(size_t)optimum.predictIndex[k * K + t]], (double)optimum.predictScore[k * K + t]);
+            line += num;
+        }
+        listed += optimum.predictCount[k];
+        line += '\n';
+        out.write(line.data(), (std::streamsize)line.size());
+    }
+    return "wrote " + std::to_string(listed) + " predicted links of " + std::to_string(kept) + " vertices to " + outputFolder + "/" + file;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1,7 +1,8 @@
 // geglove -c <config.yml> : the reference's CLI (J/Main.java:133-160) over the MI355X library.
 // Same single flag, same settings banner, same output files ./out/<name>.{vectors,dict}.tsv
 // (and <name>.neighbors.tsv with `device: { neighbors: K }`, <name>.holdout.tsv with `device: { holdout: F }`,
-// <name>.rank.tsv with `device: { rank: Q }`, <name>.clusters.tsv with `device: { clusters: K }`).
+// <name>.rank.tsv with `device: { rank: Q }`, <name>.clusters.tsv with `device: { clusters: K }`,
+// <name>.links.tsv with `device: { predict: K }`).
 #include <ctime>
 #include "ge_host.hpp"
 
@@ -90,6 +91,11 @@ static void runProgram(const Configuration &given) {                        // J
         split->rankSet(config.device.rank, rI, rJ, fPtr, fIdx);
         optimizer->rank(rI, rJ, fPtr, fIdx, optimum);
     }
+    if (config.predicting()) {                  // likewise, while the handle lives
+        std::vector<int32_t> pI, fIdx; std::vector<int64_t> fPtr;
+        predictSet(config, bca, pI, fPtr, fIdx);
+        if (!pI.empty()) optimizer->predict(pI, fPtr, fIdx, pI, (int32_t)config.device.predict, optimum);
+    }
     {
         char b[120];
         std::snprintf(b, sizeof b, "Finished optimization with final cost: %.12g", optimum.finalCost);
@@ -101,6 +107,7 @@ static void runProgram(const Configuration &given) {                        // J
     log_info("EmbeddingTextWriter", "wrote " + std::to_string(n) + " vectors to out/" + writer.vectorsFile());
     if (split) log_info("Holdout", writeHoldout(config, optimum, outFileName, "out"));
     if (split && config.ranking()) log_info("Rank", writeRank(config, optimum, outFileName, "out"));
+    if (config.predicting()) log_info("Predict", writeLinks(config, optimum, bca, outFileName, "out"));
     if (config.writingNeighbors()) {
         std::string warning;
         const std::string done = writeNeighbors(config, optimum, bca, outFileName, "out", warning);

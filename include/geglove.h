@@ -799,6 +799,55 @@ int32_t   ge_rank_summary_size(void);
 void      ge_rank_destroy(ge_rank *r);     /* before the ge_glove it was created for */
 
 /* ------------------------------------------------------------------------------------------
+ * Prediction: which columns does the model expect in row I[k]?  The columns at places 1, 2, .., K of the order that
+ * ge_glove_rank_* measures places in -- the missing links of a trained graph embedding.  The reference has no counterpart, so
+ * these are product semantics.  A prediction set is n query rows I[k], k = 0 .. n-1 (rows may repeat), with three optional parts:
+ *   filter     lists F_k exactly as for ge_glove_rank_create: filter_ptr[n + 1] (ascending offsets) into filter_idx, the ids of
+ *              a list in [0, V) and strictly ascending; filter_ptr == NULL: no filter.
+ *   subset     a candidate set S shared by all queries: n_subset strictly ascending ids in [0, V), as the subset of
+ *              ge_nn_create; NULL: all V columns (n_subset is ignored).
+ *   exclude_self   non-zero: column I[k] is not a candidate of query k.
+ *   score      z(k, c) is the z of the Ranking section: the fp32 fmaf chain from 0.0f over ascending d of
+ *              focus[I[k]][d] * context[c][d], plus cBias[c] in one fp32 add; a NaN z counts, and is reported, as -inf; fBias is
+ *              left out.  Rows are read where the handle keeps them, by the rules of ge_glove_eval_*: every mode, records,
+ *              packed records, a shard's rebased focus rows, bf16 rows widened exactly and the fp32 master row when
+ *              hub_index[c] >= 0.  A score depends on its two rows and the bias only: not on the tile, the grid or the batch.
+ *   candidates C_k = S \ F_k \ ({I[k]} if exclude_self), ordered by the total order of ge_nn_*: z descending as fp32 compares
+ *              (so -0 = +0), equal z by ascending column id.  A filter id outside S is legal and ignored; an empty C_k is legal.
+ *   result     for a run with 1 <= K <= 128: out_count[k] = min(K, |C_k|); out_index[k * K + t], out_score[k * K + t] = the
+ *              t-th candidate of that order and its z, t < out_count[k]; the remaining slots hold (-1, -inf).  A real
+ *              candidate whose z is -inf comes before the fill.  So ge_glove_rank_run on the pair (I[k], out_index[k * K + t])
+ *              with the list F_k (plus I[k] under exclude_self; S = all columns) returns rank t + 1 and the same score bits.
+ *   bytes      a function of the input alone: no floating-point atomics, no order-dependent selection.
+ *   pure read  no trainer table is written; neither the RNG state nor the permutation is touched.
+ * Limits, checked on the host before any device work (GE_ERR_ARG): 1 <= n < 2^31; 1 <= dim <= 1024; I[k] inside the handle's
+ * owned rows [row_begin, row_end); every filter id in [0, V); lists strictly ascending; filter_ptr[0] == 0 and filter_ptr
+ * non-decreasing; fewer than 2^35 filter entries in all; the subset strictly ascending, in [0, V) and n_subset >= 1;
+ * 1 <= K <= 128; no null mandatory argument.  (What needs no handle -- the null arguments, n, the shape and order of the lists
+ * and of the subset, ids below 0, K -- is refused first, so without a device as well.)
+ * Every handle mode is supported.  The set is uploaded once at creation (filter lists translated to candidate positions);
+ * ge_glove_predict_run may be called after any epoch and re-stages each time, runs on the trainer handle's stream and is blocking.
+ * Device memory: the tables are NOT read in place.  Every run stages the n query focus rows and the |S| candidate context rows
+ * into dense fp32 buffers of row length D4 = dim rounded up to 4, so a set holds (|S| + n) * D4 * 4 bytes + 4 |S| (biases) +
+ * 4 |S| (the subset, when given) + 16 n + 4 per filter entry inside S until ge_predict_destroy.  A run holds, while it lasts,
+ * the partial lists of its candidate ranges (8 K bytes per query and range, at most 128 MB: more queries go in batches, each
+ * sized by the range count of its own grid) and 8 K + 4 bytes of results per query of a batch.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct ge_predict ge_predict;
+ge_status ge_glove_predict_create(ge_glove *h, const int32_t *I, int64_t n,
+                                  const int64_t *filter_ptr, const int32_t *filter_idx,
+                                  const int32_t *subset, int64_t n_subset, int32_t exclude_self, ge_predict **out);
+/* out_index: HOST int32[n * K], out_score: HOST float[n * K], out_count: HOST int32[n]; each may be NULL. */
+ge_status ge_glove_predict_run(ge_predict *p, int32_t K, int32_t *out_index, float *out_score, int32_t *out_count);
+/* Device time of the last run's kernels, split into staging, score-and-select and the merge (hipEvents around them; copies
+ * not counted), in milliseconds; 0 = none ran.  Any out pointer may be NULL. */
+ge_status ge_predict_last_kernel_ms(const ge_predict *p, float *stage_ms, float *select_ms, float *merge_ms);
+/* *n = query rows; *candidates = |S|; *dim; *ranges = the candidate ranges the last run's grid had (0 before the first run: the
+ * results do not depend on it).  Any out pointer may be NULL. */
+ge_status ge_predict_get(const ge_predict *p, int64_t *n, int64_t *candidates, int32_t *dim, int32_t *ranges);
+void      ge_predict_destroy(ge_predict *p);   /* before the ge_glove it was created for */
+
+/* ------------------------------------------------------------------------------------------
  * Clustering: which vertices belong together?  Lloyd's k-means over a table of vectors, on one device.  The reference stops at
  * the vectors file and has no counterpart, so these are product semantics:
  *   indexed rows  as the nearest-neighbour index: host rows with an optional strictly ascending subset, or the vectors of a

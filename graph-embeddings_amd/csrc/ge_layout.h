@@ -14,6 +14,12 @@
 //     rows only, rows ascending and inside a row in slot order.  The group's columns stay resident in the worker while each
 //     focus row streams through once.  bA = focus row, bB = slot of the column in its group, cmeta = the group; tcols / tlim hold
 //     every group's column ids (-1: unused slot) and their flush limits.  The H part then holds the other hub columns only.
+//   * P part (hub panels), in front of everything when the handle has them: four consecutive FULL groups 4p .. 4p+3
+//     form panel p.  A panel chunk is a range of whole focus rows, ascending, in which each of the four groups has <= 128 nonzeros;
+//     the four waves of a workgroup walk it as a pipeline, one group each.  The positions are those of the T part (group-major,
+//     then row, then slot); the panel chunks are no part of the chunk table -- they have a queue of their own -- but are described
+//     by prow0 / prows (their focus rows) and ppos (panel, then first position and length per group).  Groups that fill no panel
+//     stay tile chunks.
 // Per position: bA = resident row id (j in H, i in R), bB = streamed row id, L = log term (fp64), W = weight (fp32),
 // border = index of the nonzero in the caller's arrays.
 #pragma once
@@ -41,6 +47,9 @@ struct LayoutRequest {
     int32_t tile_g;          // hub tiles: columns per group (0: the handle's kernel has no tile walk, never build them)
     int32_t tile_force;      // 1: every group of >= 2 hub columns becomes tiles (GE_LAYOUT_HUB_TILES); 0: columns with count >= rows / 8
     int32_t tile_workers;    // sequential workers in flight when the tile kernel runs (`workers` holds when no tile is built)
+    int32_t panels;          // 1: full groups of tile columns are walked as hub panels, four groups to a panel
+    int32_t panel_blocks;    // > 0: that many workgroups start in the panel loop; 0: the panels' share of the epoch's time
+    int32_t blocks;          // workgroups of the tile kernel's launch (what panel_blocks is a share of)
 };
 
 struct BlockedLayout {
@@ -55,6 +64,10 @@ struct BlockedLayout {
     int64_t P = 0, n_chunks = 0, n_hchunks = 0;      // n_hchunks: column-major hub chunks, [n_tchunks, n_tchunks + n_hchunks)
     int64_t n_tchunks = 0, tile_nnz = 0, tile_visits = 0;    // tile chunks, their nonzeros, (focus row, group) pairs with a nonzero
     int32_t tile_g = 0, tile_cols = 0, n_tgroups = 0;
+    int32_t *prow0 = nullptr, *prows = nullptr, *ppos = nullptr;      // hub panels: see above
+    int64_t n_pchunks = 0, panel_nnz = 0, panel_visits = 0;           // panel chunks, their nonzeros, (focus row, panel) pairs with a nonzero
+    int32_t n_panels = 0, panel_cols = 0, panel_blocks = 0;           // panel_blocks: workgroups that start in the panel loop
+    std::vector<int32_t> host_prow0, host_ppos;                       // host copies (ge_glove_epoch_order)
     int32_t workers = 0;             // the worker count the hub threshold and the flush limits were computed for
     // what was decided
     int32_t hot_cols = 0; int64_t hot_nnz = 0, hot_threshold = 0;

@@ -75,6 +75,14 @@ struct GloveParams {
     // hub tiles (k_epoch_tiles; behind everything k_adagrad_runs reads, whose argument offsets stay what they were)
     int64_t n_tchunks;        // blocked order: the first n_tchunks chunks are hub tiles (0 for every other kernel)
     const int32_t *tcols, *tlim;   // per group and slot: the column id (-1: unused) and its flush limit
+    // hub panels (k_epoch_panels; behind everything the other two kernels read)
+    int64_t n_pchunks;        // panel chunks of the epoch: a queue of their own (0 for every other kernel)
+    int32_t n_panel_blocks;   // the blocks below this one start in the panel loop, the others join it when the main queue is empty
+    uint32_t pbij_mask, pbij_shift;      // the keyed bijection over the panel tickets (same keys as the main queue's)
+    unsigned long long *pqueue;          // next panel ticket (zeroed with the main counter)
+    const int32_t *prow0;     // per panel chunk: where its focus rows start in prows (n_pchunks + 1 entries)
+    const int32_t *prows;     // the focus rows of every panel chunk, ascending
+    const int32_t *ppos;      // per panel chunk: panel, then first position and length of each of its four groups' nonzeros (9 entries)
 };
 
 // The Hogwild kernel reads (l, w) instead of X: X never changes, so the fp64 log / sqrt run once
@@ -266,6 +274,16 @@ template <int W> __device__ __forceinline__ void load_to_lds(__amdgpu_buffer_rsr
 // s_waitcnt immediate (gfx9 layout) that waits until at most n vector-memory instructions are outstanding and for nothing else
 constexpr int wait_vmcnt(int n) { return (n & 15) | ((n >> 4) << 14) | 0x0F70; }
 
+// A workgroup barrier that orders LDS accesses only: this wave's LDS operations are complete (lgkmcnt(0)) before it arrives, its
+// vector-memory instructions stay in flight -- __syncthreads() would wait for those too (its fence covers global memory), and with
+// them for the focus pair that stage 0 of the panel pipeline has requested for the NEXT step.
+__device__ __forceinline__ void lds_barrier() {
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_waitcnt(0xC07F);       // lgkmcnt(0) and nothing else
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
+
 constexpr int RUN_CHUNK = 128;            // nonzeros per worker chunk (2 per lane)
 constexpr int KEY_PAD = 0x7FFFFFFF;       // sorts last; marks the unused tail of the last chunk
 constexpr int TILE_N_AFTER = 4;           // tile_chunk: vector-memory instructions behind a focus pair's request when its image is read
@@ -280,11 +298,27 @@ constexpr int TILE_N_AFTER = 4;           // tile_chunk: vector-memory instructi
 // touches it) and is read from there by every update -- the G pairs take 16 G registers, the scalars none.
 // A column is published when it has taken its flush limit of updates since it was read, and re-read behind the publish, exactly
 // as a cut hub run; at the end of the chunk every column touched since its last read is published.
-template <int G>
+// Hub panels: the same walk as one stage of a pipeline.  The four waves of a workgroup hold the four groups of a
+// panel; a focus pair enters at wave 0 from memory, is handed from wave to wave through an LDS image and leaves from wave 3 to
+// memory.  Where the pair comes from and where it goes is a compile-time choice (SRC, SINK); a stage whose SRC or SINK is an LDS
+// image walks the rows of `pl` (every row of the panel chunk, whether this group has a nonzero there or not) with one block barrier
+// per step, `pl.lag` steps behind wave 0.
+enum { PAIR_MEM = 0, PAIR_LDS = 1 };
+struct PanelLink {
+    const int32_t *rows;      // LDS: the focus rows of the panel chunk, ascending
+    int32_t n_rows;           // read from LDS by every wave of the block: the same number in all four
+    int32_t lag;              // this stage works on row t - lag at step t (its wave in the block)
+    float *nextA, *nextB;     // SINK = PAIR_LDS: the two images of the next stage
+};
+template <int G, int SRC, int SINK>
 __device__ __forceinline__ void tile_chunk(const GloveParams &p, const int32_t c_lo, const int32_t c_len, const int32_t grp,
-                                           float *const setA, float *const setB, float *const tr_c, float *const tr_g, double &cost_acc) {
+                                           float *const setA, float *const setB, float *const tr_c, float *const tr_g,
+                                           int32_t *const stg, double &cost_acc, const PanelLink &pl, const int lane) {
+    constexpr bool PIPE = SRC == PAIR_LDS || SINK == PAIR_LDS;
+    // vector-memory instructions behind a focus pair's request when its image is read: the next row's request, and in front of it
+    // the two stores that ended the previous row where this stage stores (see walk_row)
+    constexpr int N_AFTER = SINK == PAIR_MEM ? TILE_N_AFTER : TILE_N_AFTER - 2;
     static_assert(G >= 2 && G <= 8, "two to eight resident columns");
-    const int lane = threadIdx.x & 63;
     const int32_t D = p.D, DS = p.DS;
     const uint32_t row_bytes = (uint32_t)p.RW * 4u;
     const int bl_lane = (D / 4) & 63;                    // the lane that holds element [D], the bias
@@ -296,11 +330,13 @@ __device__ __forceinline__ void tile_chunk(const GloveParams &p, const int32_t c
     // ---- stage: focus row, slot, weight and log term of the chunk's nonzeros into this wave's LDS strip (the chunk is in walk order:
     // nothing to sort).  The walk reads them back at wave-uniform addresses, so they take no vector register -- and no scalar
     // load from memory per nonzero either, whose latency a row of two or three nonzeros cannot hide (measured).
-    __shared__ int32_t s_stage[4][5 * RUN_CHUNK];
-    int32_t *const stg = s_stage[threadIdx.x >> 6];
+    // (the strip is the caller's: a __shared__ array in here would exist once per instance of this template; the lane index goes
+    // through an empty asm so that the strip's addresses are computed here, per chunk, and not held in registers across the kernel)
+    int s_lane = lane;
+    asm volatile("" : "+v"(s_lane));
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-        const int e = q * 64 + lane;
+        const int e = q * 64 + s_lane;
         if (e < c_len) {
             const int64_t k = (int64_t)c_lo + e;
             const long long lb = __builtin_bit_cast(long long, p.L[k]);
@@ -322,8 +358,10 @@ __device__ __forceinline__ void tile_chunk(const GloveParams &p, const int32_t c
         load_to_lds<16>(make_rsrc(p.gsf + (int64_t)row * DS, rbytes), img + IMG_G, lane * 16);
         asm volatile("" ::: "memory");
     };
-    int32_t n_row = row_at(0);
-    request(setA, n_row, true);
+    int32_t n_row = 0;
+    if constexpr (!PIPE) n_row = row_at(0);
+    else if constexpr (SRC == PAIR_MEM) n_row = rfl(pl.rows[0]);
+    if constexpr (SRC == PAIR_MEM) request(setA, n_row, true);
 
     // ---- the G resident pairs ----
     float4 a[G], ga[G], a0[G], ga0[G];
@@ -438,23 +476,36 @@ __device__ __forceinline__ void tile_chunk(const GloveParams &p, const int32_t c
     // One focus row.  CUR (0 / 1) names the image that holds its pair (a compile-time choice, as in epoch_walk's step: the
     // compiler then knows that the request for the other image does not touch the one read here).
     int pos = 0;
-    auto walk_row = [&](auto CUR) {
-        const int32_t row = n_row;
-        int nxt = pos + 1;                               // where the row ends, and the row behind it
+    auto walk_row = [&](auto CUR, const int ri) {
+        int32_t row;
+        int nxt;                                         // where the row ends, and the row behind it
         bool more;
-        for (;;) {
-            more = nxt < c_len;
-            n_row = more ? row_at(nxt) : 0;
-            if (!more || n_row != row) break;
-            ++nxt;
+        if constexpr (!PIPE) {
+            row = n_row;
+            nxt = pos + 1;
+            for (;;) {
+                more = nxt < c_len;
+                n_row = more ? row_at(nxt) : 0;
+                if (!more || n_row != row) break;
+                ++nxt;
+            }
+        } else {                                         // the rows are the panel chunk's; this group may have nothing in one
+            row = rfl(pl.rows[ri]);
+            nxt = pos;
+            while (nxt < c_len && row_at(nxt) == row) ++nxt;
+            more = ri + 1 < pl.n_rows;
+            if constexpr (SRC == PAIR_MEM) n_row = more ? rfl(pl.rows[ri + 1]) : 0;
         }
         const float *const img = decltype(CUR)::value ? setB : setA;
-        request(decltype(CUR)::value ? setA : setB, n_row, more);
-        // Counted by hand (see epoch_walk's step): memory instructions complete in order, and behind this image's request at
-        // least TILE_N_AFTER more have been issued on every path -- the two stores that ended the previous row (before the
-        // first row: the 2 G loads of the resident pairs), then the two loads of the request just above.  Publishes and
-        // re-reads in between only add to them.
-        __builtin_amdgcn_s_waitcnt(wait_vmcnt(TILE_N_AFTER));
+        if constexpr (SRC == PAIR_MEM) {
+            request(decltype(CUR)::value ? setA : setB, n_row, more);
+            // Counted by hand (see epoch_walk's step): memory instructions complete in order, and behind this image's request at
+            // least N_AFTER more have been issued on every path -- where this stage stores its pair, the two stores that ended the
+            // previous row (before the first row: the 2 G loads of the resident pairs); then the two loads of the request just
+            // above.  Publishes and re-reads in between only add to them.
+            __builtin_amdgcn_s_waitcnt(wait_vmcnt(N_AFTER));
+        }
+        // (SRC = PAIR_LDS: the previous stage wrote the image one step ago, and the block barrier that ended that step lies between)
         asm volatile("" ::: "memory");
         b = *reinterpret_cast<const float4 *>(img + lane * 4);
         gb = *reinterpret_cast<const float4 *>(img + IMG_G + lane * 4);
@@ -472,14 +523,41 @@ __device__ __forceinline__ void tile_chunk(const GloveParams &p, const int32_t c
             ob = float4{0.0f, 0.0f, 0.0f, 0.0f}; ogb = ob;
             if (is_bl) { ob.x = bb; ogb.x = gbb; }
         }
-        buf_store<4>(ob, make_rsrc(p.focus + (int64_t)row * DS, row_bytes), lane * 16);
-        buf_store<4>(ogb, make_rsrc(p.gsf + (int64_t)row * DS, row_bytes), lane * 16);
+        if constexpr (SINK == PAIR_MEM) {
+            buf_store<4>(ob, make_rsrc(p.focus + (int64_t)row * DS, row_bytes), lane * 16);
+            buf_store<4>(ogb, make_rsrc(p.gsf + (int64_t)row * DS, row_bytes), lane * 16);
+        } else {                                         // the image the next stage reads one step from now
+            float *const out = decltype(CUR)::value ? pl.nextB : pl.nextA;
+            *reinterpret_cast<float4 *>(out + lane * 4) = ob;
+            *reinterpret_cast<float4 *>(out + IMG_G + lane * 4) = ogb;
+        }
         asm volatile("" ::: "memory");
         pos = nxt;
     };
-    while (pos < c_len) {
-        walk_row(std::integral_constant<int, 0>{});
-        if (pos < c_len) walk_row(std::integral_constant<int, 1>{});
+    constexpr std::integral_constant<int, 0> IMG_A{};
+    constexpr std::integral_constant<int, 1> IMG_B{};
+    if constexpr (!PIPE) {
+        while (pos < c_len) {
+            walk_row(IMG_A, 0);
+            if (pos < c_len) walk_row(IMG_B, 0);
+        }
+    } else {
+        // The pipeline: n_rows + 3 steps, one block barrier each.  This stage idles `lag` steps, walks the n_rows rows -- row ri in
+        // image ri & 1, which the previous stage filled one step earlier and refills one step later -- and idles 3 - lag steps.
+        // Every barrier below is reached lag + n_rows + (3 - lag) = n_rows + 3 times by every wave of the block: n_rows is one
+        // LDS word that all four waves read behind the same barrier, and no barrier sits under any other condition.
+        // (Only LDS travels between the stages, so the barriers order LDS alone: lds_barrier.  What the stages write to memory is
+        // ordered for the next chunk by the full barrier of the ticket draw that follows.)
+        for (int i = 0; i < pl.lag; ++i) lds_barrier();             // (i) lag barriers: see above
+        for (int ri = 0; ri < pl.n_rows; ri += 2) {
+            walk_row(IMG_A, ri);
+            lds_barrier();                                          // (ii) one per row, n_rows in all
+            if (ri + 1 < pl.n_rows) {
+                walk_row(IMG_B, ri + 1);
+                lds_barrier();                                      // (ii)
+            }
+        }
+        for (int i = pl.lag; i < 3; ++i) lds_barrier();             // (iii) 3 - lag barriers
     }
     // ---- every column touched since it was last read ----
 #pragma nounroll
@@ -495,7 +573,10 @@ __device__ __forceinline__ void tile_chunk(const GloveParams &p, const int32_t c
 //   narrowed once, with STOCHASTIC rounding (an update of 1e-5 on a value of 0.1 is far below half a bf16 ulp and
 //   would always round away).  Hub context rows keep an fp32 master copy (hub32) that their runs read and
 //   publish into with the same atomics as in the fp32 build; they never touch the bf16 table during training.
-template <int VW, int NCH, int OPT, bool EMB16, bool FAT, int TG>
+// PANELS (k_epoch_panels): the workgroup also walks the hub panel chunks of the layout, its four waves as the four stages of
+// tile_chunk's pipeline.  The panel chunks have a ticket counter of their own; a block below n_panel_blocks serves it first and the
+// main queue afterwards, every other block the other way round, so whichever queue runs dry first frees its blocks for the other.
+template <int VW, int NCH, int OPT, bool EMB16, bool FAT, int TG, bool PANELS = false>
 __device__ __forceinline__ void epoch_walk(const GloveParams &p, const int32_t n_workers) {
     using VT = typename Vec<VW>::T;
     static_assert(!EMB16 || VW == 4, "bf16 embeddings need dim % 4 == 0");
@@ -507,6 +588,7 @@ __device__ __forceinline__ void epoch_walk(const GloveParams &p, const int32_t n
     // [gradSq (D) | the bias accumulator | the bias | 2 x 0]; the bf16 row itself stays D elements wide.
     // (FAT is chosen on the host: fp32 rows whose bias lane fits the last register chunk -- a dimension that fills its 64-lane
     // chunks exactly would need one more chunk for that one lane and keeps the separate bias tables instead.)
+    int tid = (int)threadIdx.x;             // (not const: see the rounds below)
     uint32_t sr_state = 0x9E3779B9u * (uint32_t)(threadIdx.x + 1) + (uint32_t)blockIdx.x * 0x85EBCA6Bu + p.bij_key[0];
     // embedding-row access: fp32 build = plain 16-byte vectors; bf16 build = 8 bytes widened / narrowed here
     auto emb_rsrc = [&](float *base, int64_t id) {
@@ -514,8 +596,8 @@ __device__ __forceinline__ void epoch_walk(const GloveParams &p, const int32_t n
         else return make_rsrc(base + id * p.DS, (uint32_t)p.RW * 4u);
     };
     auto emb_load = [&](__amdgpu_buffer_rsrc_t rs, int q) -> VT {
-        if constexpr (EMB16) return widen_bf16x4(buf_load<2, AUX_SC1>(rs, ((threadIdx.x & 63) + q * 64) * 8));
-        else return buf_load<VW, AUX_SC1>(rs, ((threadIdx.x & 63) + q * 64) * VW * 4);
+        if constexpr (EMB16) return widen_bf16x4(buf_load<2, AUX_SC1>(rs, ((tid & 63) + q * 64) * 8));
+        else return buf_load<VW, AUX_SC1>(rs, ((tid & 63) + q * 64) * VW * 4);
     };
     auto emb_store = [&](VT v, __amdgpu_buffer_rsrc_t rs, int q) {
         if constexpr (EMB16) {
@@ -526,8 +608,8 @@ __device__ __forceinline__ void epoch_walk(const GloveParams &p, const int32_t n
             float2 raw;
             raw.x = __builtin_bit_cast(float, narrow(v.x) | (narrow(v.y) << 16));
             raw.y = __builtin_bit_cast(float, narrow(v.z) | (narrow(v.w) << 16));
-            buf_store<2>(raw, rs, ((threadIdx.x & 63) + q * 64) * 8);
-        } else buf_store<VW>(v, rs, ((threadIdx.x & 63) + q * 64) * VW * 4);
+            buf_store<2>(raw, rs, ((tid & 63) + q * 64) * 8);
+        } else buf_store<VW>(v, rs, ((tid & 63) + q * 64) * VW * 4);
     };
     constexpr float BETA1 = 0.9f, BETA2 = 0.999f, EPS = 1e-7f, OMB1 = 1 - BETA1, OMB2 = 1 - BETA2;   // Adam.java:45-53
     const float corr = OPT == GE_OPT_ADAM ? (float)p.correction : p.lr;      // Adam.java:84 | AMSGrad.java:133 uses lr itself
@@ -540,7 +622,6 @@ __device__ __forceinline__ void epoch_walk(const GloveParams &p, const int32_t n
         // tests/kernel_model.py can restate this arithmetic bit for bit; __fsqrt_rn is the 1-ulp v_sqrt_f32 in this toolchain
         return corr * m * (1.0f / (__builtin_sqrtf(v) + EPS));
     };
-    const int lane = threadIdx.x & 63;
     const int32_t D = p.D;
     const int32_t DS = p.DS;
     const uint32_t row_bytes = (uint32_t)p.RW * 4u;
@@ -551,7 +632,9 @@ __device__ __forceinline__ void epoch_walk(const GloveParams &p, const int32_t n
     constexpr int BIAS_C = EMB16 ? 1 : 0;
     const float lr = p.lr;
     const int wave = rfl((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
-    if (wave >= n_workers) return;          // workers pull chunks of the epoch order from one queue
+    // workers pull chunks of the epoch order from one queue.  (PANELS: every block holds a worker, and all four of its waves stay
+    // for the panel chunks -- the block barriers there need them; only the ordinary loop is limited to the workers.)
+    if constexpr (!PANELS) { if (wave >= n_workers) return; }
     const int64_t n_chunks = p.n_chunks;
     __shared__ float s_tr[4][2][NCH * 64 * VW];       // per-wave strip for the atomic flush (no block barrier)
     // The streamed rows of the NEXT nonzero land in LDS, not in registers (buffer_load ... lds, 16 bytes per lane): nothing
@@ -568,12 +651,77 @@ __device__ __forceinline__ void epoch_walk(const GloveParams &p, const int32_t n
     constexpr int IMG_B = IMG_H + (MOM ? NCH * IMG : 0);                             // three 256-byte slots for the bias scalars (not FAT)
     constexpr int SET_FLOATS = IMG_B + (FAT ? 0 : 3 * 64);
     __shared__ float s_setA[4 * SET_FLOATS], s_setB[4 * SET_FLOATS];
-    float *const setA = s_setA + (threadIdx.x >> 6) * SET_FLOATS, *const setB = s_setB + (threadIdx.x >> 6) * SET_FLOATS;
     double cost_acc = 0.0;
+    __shared__ int32_t s_stage[TG > 0 ? 4 : 1][TG > 0 ? 5 * RUN_CHUNK : 1];      // tile_chunk's strip of staged nonzeros, one per wave
+    const PanelLink no_link{nullptr, 0, 0, nullptr, nullptr};
+
+    // The block serves its two queues one after the other (PANELS; every other kernel: the main queue alone).  `panels_first`
+    // depends on the block's index only, so all four waves take the same branch in both rounds.
+    const bool panels_first = PANELS && (int32_t)blockIdx.x < p.n_panel_blocks;
+    // What either loop derives from the thread's index is derived inside its round: computed once at the kernel's entry it would be
+    // held across the other loop, which has no register to spare for it (PANELS; every other kernel: the same values as ever).
+#pragma nounroll
+    for (int round = 0; round < (PANELS ? 2 : 1); ++round) {
+    if constexpr (PANELS) asm volatile("" : "+v"(tid));
+    if constexpr (PANELS) {
+    if ((round == 0) == panels_first) {
+        static_assert(!PANELS || TG == 4, "a panel is four groups of four columns, one per wave of the block");
+        const int wib = rfl(tid >> 6);
+        // the focus rows of one panel chunk: each has a nonzero in one of four groups of <= RUN_CHUNK nonzeros
+        __shared__ int32_t s_prow[4 * RUN_CHUNK];
+        __shared__ int32_t s_pticket, s_pn;
+        __shared__ double s_pcost[4];
+        // A block that comes from the main queue: its waves (those that never were workers included) meet here.  Reached once,
+        // by every wave of the block: the round and the branch above are the same for all of them.
+        __syncthreads();
+        const int32_t n_pchunks = (int32_t)p.n_pchunks;
+        for (;;) {
+            // (the word is free again: every wave read it before barrier (b) of the previous iteration, which thread 0 has passed)
+            if (tid == 0) {
+                const unsigned long long t = atomicAdd(p.pqueue, 1ull);
+                s_pticket = t >= (unsigned long long)n_pchunks ? -1 : (int32_t)t;
+            }
+            // (a) once per iteration.  The loop ends at the break below, on one LDS word that all four waves read behind this
+            // barrier, so all of them leave in the same iteration.
+            __syncthreads();
+            const int32_t tk = rfl(s_pticket);
+            if (tk < 0) break;
+            uint32_t x = (uint32_t)tk;
+            do { x = bij_mix(x, p.pbij_mask, p.pbij_shift, p.bij_key); } while (x >= (uint32_t)n_pchunks);
+            const int32_t pc = rfl((int)x);
+            const int32_t r0 = rfl(p.prow0[pc]), nr = rfl(p.prow0[pc + 1]) - r0;
+            if (tid < nr) s_prow[tid] = p.prows[r0 + tid];                       // 256 threads, at most 4 * RUN_CHUNK = 512 rows
+            if (tid + 256 < nr && tid + 256 < 4 * RUN_CHUNK) s_prow[tid + 256] = p.prows[r0 + tid + 256];
+            if (tid == 0) s_pn = nr < 4 * RUN_CHUNK ? nr : 4 * RUN_CHUNK;
+            // (b) once per iteration that passed the break above (the same iterations in every wave): the rows and their number
+            // are in LDS for all four stages
+            __syncthreads();
+            const int32_t *const pp = p.ppos + (int64_t)pc * 9;
+            const int32_t grp = rfl(pp[0]) * 4 + wib, c_lo = rfl(pp[1 + 2 * wib]), c_len = rfl(pp[2 + 2 * wib]);
+            const int nx = wib < 3 ? wib + 1 : 0;          // (wave 3 has no next stage: it stores to memory)
+            const PanelLink pl{s_prow, rfl(s_pn), wib, s_setA + nx * SET_FLOATS, s_setB + nx * SET_FLOATS};
+            float *const tr_c = s_tr[wib][0], *const tr_g = s_tr[wib][1];
+            float *const setA = s_setA + wib * SET_FLOATS, *const setB = s_setB + wib * SET_FLOATS;
+            // the stage of this wave: a compile-time source and sink each (the barriers inside are counted in tile_chunk)
+            if (wib == 0) tile_chunk<TG, PAIR_MEM, PAIR_LDS>(p, c_lo, c_len, grp, setA, setB, tr_c, tr_g, s_stage[wib], cost_acc, pl, tid & 63);
+            else if (wib < 3) tile_chunk<TG, PAIR_LDS, PAIR_LDS>(p, c_lo, c_len, grp, setA, setB, tr_c, tr_g, s_stage[wib], cost_acc, pl, tid & 63);
+            else tile_chunk<TG, PAIR_LDS, PAIR_MEM>(p, c_lo, c_len, grp, setA, setB, tr_c, tr_g, s_stage[wib], cost_acc, pl, tid & 63);
+        }
+        // The four stages' costs go out through wave 0, summed in stage order: with one block the epoch's cost is then the same
+        // bits every run.  (c) once, behind the loop that every wave leaves in the same iteration.
+        s_pcost[wib] = cost_acc;
+        __syncthreads();
+        if (wib == 0) cost_acc = ((s_pcost[0] + s_pcost[1]) + s_pcost[2]) + s_pcost[3];
+        else cost_acc = 0.0;
+        continue;
+    }
+    if (wave >= n_workers) continue;       // not a worker: nothing to do in the main queue
+    }
+    const int lane = tid & 63;
+    float *const setA = s_setA + (tid >> 6) * SET_FLOATS, *const setB = s_setB + (tid >> 6) * SET_FLOATS;
     bool inr[NCH];                          // lane holds real elements of a row (D % VW == 0)
 #pragma unroll
     for (int q = 0; q < NCH; ++q) inr[q] = (lane + q * 64) * VW < D;
-
     for (;;) {
         unsigned long long ticket = 0;
         if (lane == 0) ticket = atomicAdd(p.queue, 1ull);
@@ -601,7 +749,8 @@ __device__ __forceinline__ void epoch_walk(const GloveParams &p, const int32_t n
             if constexpr (TG > 0) {
                 static_assert(VW == 4 && NCH == 1 && OPT == GE_OPT_ADAGRAD && !EMB16 && FAT, "hub tiles: fp32 AdaGrad fat rows of one register chunk");
                 if (chunk < p.n_tchunks) {           // a hub tile: c_meta = its group
-                    tile_chunk<TG>(p, c_lo, c_len, c_meta, setA, setB, s_tr[threadIdx.x >> 6][0], s_tr[threadIdx.x >> 6][1], cost_acc);
+                    tile_chunk<TG, PAIR_MEM, PAIR_MEM>(p, c_lo, c_len, c_meta, setA, setB, s_tr[tid >> 6][0], s_tr[tid >> 6][1],
+                                                       s_stage[tid >> 6], cost_acc, no_link, lane);
                     continue;
                 }
             }
@@ -727,7 +876,7 @@ __device__ __forceinline__ void epoch_walk(const GloveParams &p, const int32_t n
                 // Publish the run's delta with float atomics.  Lane L holds elements [VW*L, VW*L+VW);
                 // staged through this wave's LDS strip so that every atomic wave-instruction covers 64
                 // CONSECUTIVE dwords (256 B = four 64-B memory-side requests instead of sixteen).
-                float *tr_c = s_tr[threadIdx.x >> 6][0], *tr_g = s_tr[threadIdx.x >> 6][1];
+                float *tr_c = s_tr[tid >> 6][0], *tr_g = s_tr[tid >> 6][1];
 #pragma unroll
                 for (int q = 0; q < NCH; ++q) {
                     VT dc, dg;
@@ -1018,7 +1167,8 @@ __device__ __forceinline__ void epoch_walk(const GloveParams &p, const int32_t n
             if (pos + 1 < n_valid) step(pos + 1, SET_B);
         }
     }
-    if (lane == 0 && cost_acc != 0.0) atomicAdd(p.cost_out, cost_acc);
+    }
+    if ((tid & 63) == 0 && cost_acc != 0.0) atomicAdd(p.cost_out, cost_acc);
 }
 
 template <int VW, int NCH, int OPT, bool EMB16, bool FAT>
@@ -1034,6 +1184,11 @@ constexpr int TILE_G = 4;                 // columns per hub-tile group: the one
 template <int G>
 __global__ __launch_bounds__(256, 3) void k_epoch_tiles(GloveParams p, int32_t n_workers) {
     epoch_walk<4, 1, GE_OPT_ADAGRAD, false, true, G>(p, n_workers);
+}
+// The epoch of a handle whose layout has hub panels: the walk above, and the panel chunks on the four waves of a
+// workgroup.  The same register budget: a stage of the pipeline holds what a tile chunk holds.
+__global__ __launch_bounds__(256, 3) void k_epoch_panels(GloveParams p, int32_t n_workers) {
+    epoch_walk<4, 1, GE_OPT_ADAGRAD, false, true, TILE_G, true>(p, n_workers);
 }
 
 // Placement probe: what an epoch does to a record table -- whole records read and written back at random rows, sc1 like the trainer's
@@ -1101,7 +1256,7 @@ struct ge_glove {
     float *dX = nullptr;
     double *dL = nullptr;             // Hogwild: log term per nonzero
     float *dW = nullptr;              // Hogwild: weight per nonzero
-    double *dcost = nullptr;          // Hogwild accumulator (+ the chunk queue word behind it)
+    double *dcost = nullptr;          // Hogwild accumulator (+ the chunk queue word and the panel queue word behind it)
     float *djob = nullptr;            // deterministic: per-job fp32 costs
     std::vector<int32_t> perm;        // host copy, GE_SHUFFLE_JAVA
     ge::JavaRandom rng{0};
@@ -1117,6 +1272,7 @@ struct ge_glove {
     bool blocked = false;             // Hogwild + DEVICE shuffle: the layout of ge_layout.h
     ge::BlockedLayout lay;            // its device arrays (bA, bB, L, W, border, cstart, cmeta)
     int64_t n_chunks = 0, n_hchunks = 0, n_tchunks = 0;     // n_hchunks: column-major hub chunks, behind the n_tchunks hub tiles
+    int64_t n_pchunks = 0;            // hub panel chunks: a queue of their own, in front of the chunk table's
     int flush_every = RUN_CHUNK;
     bool emb16 = false;               // focus/context stored as bf16 (tab[] pointers then address uint16 data)
     bool fat = false;                 // Hogwild: a row is D + 4 floats with its bias at [D] (pick_hogwild); tab[*BIAS] are null
@@ -1222,6 +1378,9 @@ void fill_params(const ge_glove *h, GloveParams &p, int32_t iteration) {
     p.bA = h->lay.bA; p.bB = h->lay.bB; p.cstart = h->lay.cstart; p.cmeta = h->lay.cmeta; p.n_chunks = h->n_chunks;
     p.n_tchunks = h->n_tchunks; p.n_hchunks = h->n_tchunks + h->n_hchunks; p.tcols = h->lay.tcols; p.tlim = h->lay.tlim;
     p.ticket_end = h->n_chunks;
+    p.n_pchunks = h->n_pchunks; p.n_panel_blocks = h->lay.panel_blocks; p.pqueue = p.queue + 1;
+    p.prow0 = h->lay.prow0; p.prows = h->lay.prows; p.ppos = h->lay.ppos;
+    bijection_width(h->n_pchunks, &p.pbij_mask, &p.pbij_shift);
     p.blocked = h->blocked ? 1 : 0; p.hot_enabled = h->cfg.hot_columns != GE_HOT_NONE; p.flush_every = h->flush_every;
     bijection_width(h->blocked ? h->n_chunks : h->cfg.nnz, &p.bij_mask, &p.bij_shift);      // what the keyed bijection permutes
     bijection_keys(h->cfg.seed, iteration, p.bij_key);
@@ -1384,7 +1543,7 @@ ge_status validate_config(const ge_glove_cfg *cfg, const int32_t *I, const int32
     if (emb16 && (cfg->mode != GE_MODE_HOGWILD || cfg->shuffle != GE_SHUFFLE_DEVICE || cfg->opt != GE_OPT_ADAGRAD || cfg->dim % 4 != 0))
         return ge::fail(GE_ERR_ARG, "bf16 embeddings need mode=hogwild, shuffle=device, opt=adagrad and dim %% 4 == 0 (the reference path is fp32)");
     if (cfg->hot_columns < GE_HOT_AUTO || cfg->hot_columns > GE_HOT_ALL) return ge::fail(GE_ERR_ARG, "invalid hot_columns %d", cfg->hot_columns);
-    if (cfg->hot_theta < 0 || cfg->stale_budget < 0 || cfg->flush_every < 0 || cfg->blocks_per_cu < 0 || (cfg->layout_flags & ~127) != 0)
+    if (cfg->hot_theta < 0 || cfg->stale_budget < 0 || cfg->flush_every < 0 || cfg->blocks_per_cu < 0 || (cfg->layout_flags & ~511) != 0)
         return ge::fail(GE_ERR_ARG, "invalid tuning fields (hot_theta %g, stale_budget %g, flush_every %d, blocks_per_cu %d, layout_flags %d)",
                         (double)cfg->hot_theta, (double)cfg->stale_budget, cfg->flush_every, cfg->blocks_per_cu, cfg->layout_flags);
     int32_t rb = cfg->row_begin, re = cfg->row_end;
@@ -1545,12 +1704,26 @@ void plan_workers(ge_glove *h) { take_plan(h, plan_workers_of(h, h->hw.fn)); }
 // Hub tiles: the kernel with the tile walk exists for one lane shape; a handle of that shape that owns every focus
 // row gets tiles when GE_LAYOUT_HUB_TILES asks for them, or by default from 2^25 nonzeros on (the saving is reasoned and measured at
 // the bench size only; smaller handles keep their chunk table and their kernel).  GE_LAYOUT_NO_HUB_TILES: never.
+// (GE_LAYOUT_HUB_PANELS on a handle too small for tiles of its own asks for the tiles its panels are made of, as GE_LAYOUT_HUB_TILES
+// does -- unless GE_LAYOUT_NO_HUB_PANELS takes it back; from 2^25 nonzeros on the panels are made of the tiles the handle builds anyway)
+bool tiles_forced(const ge_glove_cfg &cfg) {
+    const bool panels_asked = (cfg.layout_flags & (GE_LAYOUT_HUB_PANELS | GE_LAYOUT_NO_HUB_PANELS)) == GE_LAYOUT_HUB_PANELS;
+    return (cfg.layout_flags & GE_LAYOUT_HUB_TILES) != 0 || (panels_asked && cfg.nnz < ((int64_t)1 << 25));
+}
 bool tiles_possible(const ge_glove *h) {
     const ge_glove_cfg &cfg = h->cfg;
     if (cfg.layout_flags & GE_LAYOUT_NO_HUB_TILES) return false;
     if (h->emb16 || cfg.opt != GE_OPT_ADAGRAD || !h->hw.fat || h->hw.vw != 4 || h->hw.nch != 1) return false;
     if (cfg.shuffle != GE_SHUFFLE_DEVICE || h->rows != cfg.vocab_size) return false;
-    return (cfg.layout_flags & GE_LAYOUT_HUB_TILES) != 0 || cfg.nnz >= ((int64_t)1 << 25);
+    return tiles_forced(cfg) || cfg.nnz >= ((int64_t)1 << 25);
+}
+// Hub panels: full groups of tile columns walked four to a workgroup.  A handle that builds tiles builds panels
+// from the same 2^25 nonzeros on (measured at the bench size only), or at any size when GE_LAYOUT_HUB_PANELS asks;
+// GE_LAYOUT_NO_HUB_PANELS: never -- the handle is then the one it was before there were panels.
+bool panels_possible(const ge_glove *h) {
+    const ge_glove_cfg &cfg = h->cfg;
+    if ((cfg.layout_flags & GE_LAYOUT_NO_HUB_PANELS) || !tiles_possible(h)) return false;
+    return (cfg.layout_flags & GE_LAYOUT_HUB_PANELS) != 0 || cfg.nnz >= ((int64_t)1 << 25);
 }
 
 // The order a Hogwild epoch visits the nonzeros in.  Device shuffle: the blocked layout of ge_layout.h, built on the device.
@@ -1581,11 +1754,15 @@ ge_status plan_epoch_layout(ge_glove *h, const int32_t *I, const int32_t *J, con
         WorkerPlan tile_plan{};
         if (tiles_possible(h)) {
             tile_plan = plan_workers_of(h, tile_fn);
-            rq.tile_g = TILE_G; rq.tile_force = (cfg.layout_flags & GE_LAYOUT_HUB_TILES) ? 1 : 0; rq.tile_workers = tile_plan.workers;
+            rq.tile_g = TILE_G; rq.tile_force = tiles_forced(cfg) ? 1 : 0; rq.tile_workers = tile_plan.workers;
+            if (panels_possible(h)) {
+                rq.panels = 1; rq.blocks = tile_plan.blocks;
+                if (const char *e = std::getenv("GE_PANEL_BLOCKS")) rq.panel_blocks = std::max(0, std::atoi(e));     // experiments: the sweep of profiles/hub_panels_bench.json
+            }
         }
         GE_CHECK(ge::build_blocked_layout(rq, I, J, X, h->stream, &h->lay));
-        if (h->lay.n_tchunks > 0) { h->hw.fn = tile_fn; take_plan(h, tile_plan); }
-        h->n_chunks = h->lay.n_chunks; h->n_hchunks = h->lay.n_hchunks; h->n_tchunks = h->lay.n_tchunks;
+        if (h->lay.n_tchunks > 0 || h->lay.n_pchunks > 0) { h->hw.fn = h->lay.n_pchunks > 0 ? (hogwild_fn)k_epoch_panels : tile_fn; take_plan(h, tile_plan); }
+        h->n_chunks = h->lay.n_chunks; h->n_hchunks = h->lay.n_hchunks; h->n_tchunks = h->lay.n_tchunks; h->n_pchunks = h->lay.n_pchunks;
         h->hot_cols = h->lay.hot_cols; h->hot_nnz = h->lay.hot_nnz; h->hot_threshold = h->lay.hot_threshold;
         h->flush_every = h->lay.flush_min;
         if (h->emb16) { h->host_hub_index.swap(h->lay.hub_index); h->n_hub = h->lay.n_hub; }
@@ -1704,7 +1881,7 @@ ge_status ge_glove_create_impl(const ge_glove_cfg *cfg, const int32_t *I, const 
 
     GE_CHECK(alloc_tables(h.get()));
     clk.lap("tables (placement search)");
-    GE_HIP(h->alloc(&h->dcost, 2));
+    GE_HIP(h->alloc(&h->dcost, 3));
     GE_HIP(h->alloc(&h->djob, (size_t)cfg->threads));
     if (h->hogwild()) {
         plan_workers(h.get());
@@ -1750,7 +1927,7 @@ ge_status ge_glove_create_coo_impl(const ge_glove_cfg *cfg, const ge_coo *coo, g
 
 // start of a Hogwild epoch on the handle's stream: cost accumulator and ticket counter zeroed, ev0 behind them
 ge_status begin_hogwild_epoch(ge_glove *h) {
-    GE_HIP(hipMemsetAsync(h->dcost, 0, 2 * sizeof(double), h->stream));
+    GE_HIP(hipMemsetAsync(h->dcost, 0, 3 * sizeof(double), h->stream));
     GE_HIP(hipEventRecord(h->ev0, h->stream));
     h->last_launches = 0;
     return GE_OK;
@@ -1839,6 +2016,21 @@ ge_status ge_glove_epoch_order_impl(ge_glove *h, int32_t iteration, int32_t *out
     }
     std::vector<std::pair<int32_t, int32_t>> ent;      // (key, original nonzero) of one chunk, in staging order
     int64_t w = 0;
+    // Panel tickets first (what a handle of one block executes): a panel chunk's rows ascending, per row its four groups in turn,
+    // inside a group the slot order the positions already have.
+    for (int64_t t = 0; t < h->n_pchunks; ++t) {
+        uint32_t x = (uint32_t)t;
+        do { x = ge::bij_mix(x, p.pbij_mask, p.pbij_shift, p.bij_key); } while ((int64_t)x >= h->n_pchunks);
+        const int32_t *pp = h->lay.host_ppos.data() + (size_t)x * 9;
+        int32_t at[4], end[4];
+        for (int g = 0; g < 4; ++g) { at[g] = pp[1 + 2 * g]; end[g] = at[g] + pp[2 + 2 * g]; }
+        for (;;) {
+            int32_t row = INT32_MAX;
+            for (int g = 0; g < 4; ++g) if (at[g] < end[g]) row = std::min(row, key[(size_t)at[g]]);
+            if (row == INT32_MAX) break;
+            for (int g = 0; g < 4; ++g) while (at[g] < end[g] && key[(size_t)at[g]] == row) out[w++] = border[(size_t)at[g]++];
+        }
+    }
     for (int64_t t = 0; t < h->n_chunks; ++t) {
         ent.clear();
         if (h->blocked) {
@@ -1954,6 +2146,11 @@ ge_status ge_glove_tile_info(ge_glove *h, int64_t out[4]) {
     out[0] = h->n_tchunks; out[1] = h->lay.tile_nnz; out[2] = h->lay.tile_g; out[3] = h->lay.tile_cols;
     return GE_OK;
 }
+ge_status ge_glove_panel_info(ge_glove *h, int64_t out[4]) {
+    if (!h || !out) return ge::fail(GE_ERR_ARG, "null argument");
+    out[0] = h->n_pchunks; out[1] = h->lay.panel_nnz; out[2] = h->lay.panel_cols; out[3] = h->n_pchunks > 0 ? h->lay.panel_blocks : 0;
+    return GE_OK;
+}
 
 ge_status ge_glove_get_info(ge_glove *h, ge_glove_info *info) {
     if (!h || !info) return ge::fail(GE_ERR_ARG, "null argument");
@@ -1973,8 +2170,10 @@ ge_status ge_glove_get_info(ge_glove *h, ge_glove_info *info) {
         const int64_t aux = h->cfg.opt == GE_OPT_ADAGRAD ? 1 : 2;                 // accumulator rows per side
         const int64_t pair = 2 * (emb + aux * acc) + (h->fat ? 0 : 2 * 4 * (1 + aux));   // load + store of a row, its accumulator row(s) and, unless fat, its scalars
         info->runs = h->lay.n_runs;
-        // a nonzero streams a pair; inside a hub tile the pair streams once per (focus row, group) instead
-        info->schedule_bytes = h->cfg.nnz * 20 + (h->cfg.nnz - h->lay.tile_nnz + h->lay.tile_visits) * pair + h->lay.n_runs * pair;
+        // a nonzero streams a pair; inside a hub tile the pair streams once per (focus row, group) instead, inside a hub panel once
+        // per (focus row, panel)
+        const int64_t streamed = h->cfg.nnz - h->lay.tile_nnz + h->lay.tile_visits - h->lay.panel_nnz + h->lay.panel_visits;
+        info->schedule_bytes = h->cfg.nnz * 20 + streamed * pair + h->lay.n_runs * pair;
     }
     return GE_OK;
 }

@@ -130,6 +130,18 @@ struct Dev {            // frees every temporary of one build
     }
 };
 
+// Workgroups that start in the panel loop: the panels' share of the epoch's TIME, so that both queues run dry together and panel
+// chunks and ordinary chunks alternate through the whole epoch.  (Hub columns trained in a phase of their own, before or behind
+// everything else, cost convergence: at C2's shape with forced panels the second epoch's cost is 4 % above the column-major walk's
+// with every workgroup starting in the panel loop, 0.2 % with 600 of 768.)  The panel loop is a dependent chain: a pipeline step
+// lasts as long as its busiest stage, so a (row, panel) visit counts the largest number of nonzeros one of the four groups has in
+// that row, a chunk three more steps, and a workgroup does one step at a time; the main queue's nonzeros go four to a workgroup at
+// a time.  PANEL_STEP_COST is a panel update's time over an ordinary one's (its focus pair comes from LDS, not from memory), fitted
+// to the two measured optima: 192 workgroups at the bench size (sweep 24 / 82 / 96 / 192 / 384) and 600 at C2's shape (500 / 600 /
+// 700 / 760 / 768); profiles/hub_panels_bench.json.  The panels' share of the schedule's BYTES, doubled -- the first guess -- gives
+// 82 at the bench size, where the panel loop is then the long pole and the epoch slower than without panels.
+constexpr double PANEL_STEP_COST = 0.8;
+
 int grid_for(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 16384)); }
 
 }  // namespace
@@ -137,8 +149,9 @@ int grid_for(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n 
 namespace ge {
 
 void BlockedLayout::release() {
-    for (void *q : {(void *)bA, (void *)bB, (void *)border, (void *)L, (void *)W, (void *)cstart, (void *)cmeta, (void *)tcols, (void *)tlim}) if (q) (void)hipFree(q);
-    bA = bB = border = cstart = cmeta = tcols = tlim = nullptr; L = nullptr; W = nullptr;
+    for (void *q : {(void *)bA, (void *)bB, (void *)border, (void *)L, (void *)W, (void *)cstart, (void *)cmeta, (void *)tcols, (void *)tlim,
+                    (void *)prow0, (void *)prows, (void *)ppos}) if (q) (void)hipFree(q);
+    bA = bB = border = cstart = cmeta = tcols = tlim = prow0 = prows = ppos = nullptr; L = nullptr; W = nullptr;
 }
 
 ge_status build_blocked_layout(const LayoutRequest &rq, const int32_t *I, const int32_t *J, const float *X,
@@ -222,6 +235,9 @@ ge_status build_blocked_layout(const LayoutRequest &rq, const int32_t *I, const 
     std::vector<int32_t> hubsR;                    // the hub columns outside the tiles, ascending: the H part
     int32_t n_tgroups = 0;
     out->n_tchunks = 0; out->tile_nnz = 0; out->tile_visits = 0; out->tile_g = 0; out->tile_cols = 0; out->n_tgroups = 0;
+    out->n_pchunks = 0; out->panel_nnz = 0; out->panel_visits = 0; out->n_panels = 0; out->panel_cols = 0; out->panel_blocks = 0;
+    out->host_prow0.clear(); out->host_ppos.clear();
+    int32_t n_panels = 0;                          // hub panels: groups [0, 4 n_panels) of the tile columns
     auto hub_threshold = [&](int32_t wk) -> int64_t {
         int64_t thr = rq.hot_columns == GE_HOT_ALL ? 0
                     : std::max<int64_t>(2, (int64_t)std::ceil(rq.hot_theta * (double)N / (double)std::max(wk, 1)));
@@ -252,8 +268,14 @@ ge_status build_blocked_layout(const LayoutRequest &rq, const int32_t *I, const 
             if (n_el >= 2) {
                 n_tgroups = (int32_t)groups;
                 tile_slot.assign((size_t)V, -1); tcols.assign((size_t)n_tgroups * G, -1); tlim.assign((size_t)n_tgroups * G, LAYOUT_CHUNK);
-                for (size_t k = 0; k < n_el; ++k) { tile_slot[(size_t)el[k]] = (int32_t)k; tcols[k] = el[k]; out->tile_nnz += cnt[(size_t)el[k]]; }
-                out->tile_g = G; out->tile_cols = (int32_t)n_el; out->n_tgroups = n_tgroups;
+                // only full panels of four full groups; what is left over stays tile chunks
+                if (rq.panels && G == 4) n_panels = (int32_t)(n_el / (size_t)G / 4);
+                for (size_t k = 0; k < n_el; ++k) {
+                    tile_slot[(size_t)el[k]] = (int32_t)k; tcols[k] = el[k];
+                    (k < (size_t)n_panels * 16 ? out->panel_nnz : out->tile_nnz) += cnt[(size_t)el[k]];
+                }
+                out->n_panels = n_panels; out->panel_cols = n_panels * 16;
+                out->tile_g = G; out->tile_cols = (int32_t)n_el - out->panel_cols; out->n_tgroups = n_tgroups;
                 workers = std::max(rq.tile_workers, 1);
             }
         }
@@ -302,7 +324,7 @@ ge_status build_blocked_layout(const LayoutRequest &rq, const int32_t *I, const 
         // The staleness rule K m <= stale_budget with the K of a tile: a worker inside ANY chunk of the group holds all its columns,
         // so K_g = group nonzeros * workers / N workers hold column j at once (not count_j * workers / N as in a column-major
         // chunk), each for m of its own updates of j.  One limit per group.
-        for (int32_t g = 0; g < n_tgroups; ++g) {
+        for (int32_t g = 4 * n_panels; g < n_tgroups; ++g) {      // (a panel's limits follow from its chunks: below, behind the sort)
             int64_t gn = 0;
             for (int s = 0; s < G; ++s) if (tcols[(size_t)g * G + s] >= 0) gn += cnt[(size_t)tcols[(size_t)g * G + s]];
             const double K = std::max(1.0, (double)gn * (double)workers / (double)std::max<int64_t>(N, 1));
@@ -334,14 +356,78 @@ ge_status build_blocked_layout(const LayoutRequest &rq, const int32_t *I, const 
 
     // ---- chunk table ----
     clk.lap("sort");
-    const int64_t nT = out->tile_nnz, nH = out->hot_nnz, nR = N - nH;      // positions: tiles [0, nT), other hubs [nT, nH), the rest
+    const int64_t nP = out->panel_nnz, nT = nP + out->tile_nnz, nH = out->hot_nnz, nR = N - nH;      // positions: panels [0, nP), tiles [nP, nT), other hubs [nT, nH), the rest
     std::vector<int32_t> cfill, cmeta;                   // per chunk: positions in it, meta
+    // P: per panel the focus rows in ascending order; a row with a nonzero in any of the four groups belongs to the chunk, and the
+    // chunk closes where the next row would take one of the groups past 128 nonzeros.  Runs: every column of the panel is loaded
+    // once per chunk; cuts are counted by k_tile_cuts over the (chunk, group) ranges, which are contiguous group by group.
+    std::vector<int32_t> prow0{0}, prows, ppos;          // see ge_layout.h
+    std::vector<int32_t> sub_start, sub_meta;            // the (chunk, group) ranges in position order, as a chunk table of their own
+    std::vector<int64_t> panel_chunks((size_t)n_panels, 0);
+    int64_t panel_steps = 0;                             // pipeline steps weighted by their busiest stage (see PANEL_STEP_COST)
+    {
+        int64_t gbase = 0;                               // first position of the panel's first group
+        for (int32_t pn = 0; pn < n_panels; ++pn) {
+            int64_t gpos[4], gn[4];
+            for (int w = 0; w < 4; ++w) {
+                gn[w] = 0;
+                for (int s = 0; s < G; ++s) gn[w] += cnt[(size_t)tcols[((size_t)pn * 4 + w) * G + s]];
+                gpos[w] = w ? gpos[w - 1] + gn[w - 1] : gbase;
+            }
+            gbase = gpos[3] + gn[3];
+            const size_t first = ppos.size() / 9;
+            int32_t fill[4] = {0, 0, 0, 0}; bool open = false;
+            auto close = [&]() {
+                if (!open) return;
+                ppos.push_back(pn);
+                for (int w = 0; w < 4; ++w) { ppos.push_back((int32_t)gpos[w]); ppos.push_back(fill[w]); gpos[w] += fill[w]; fill[w] = 0; }
+                prow0.push_back((int32_t)prows.size());
+                out->n_runs += 4 * G; ++panel_chunks[(size_t)pn];
+                open = false;
+            };
+            const int32_t *tc[4];
+            for (int w = 0; w < 4; ++w) tc[w] = tcnt.data() + ((size_t)pn * 4 + w) * (size_t)rows;
+            for (int32_t r = 0; r < rows; ++r) {
+                const int32_t c[4] = {tc[0][r], tc[1][r], tc[2][r], tc[3][r]};
+                if (!(c[0] | c[1] | c[2] | c[3])) continue;
+                if (fill[0] + c[0] > LAYOUT_CHUNK || fill[1] + c[1] > LAYOUT_CHUNK || fill[2] + c[2] > LAYOUT_CHUNK || fill[3] + c[3] > LAYOUT_CHUNK) close();
+                for (int w = 0; w < 4; ++w) fill[w] += c[w];
+                prows.push_back(rb + r); open = true; ++out->panel_visits;
+                panel_steps += std::max(std::max(c[0], c[1]), std::max(c[2], c[3]));
+            }
+            close();
+            for (int w = 0; w < 4; ++w)                  // this panel's ranges, group by group
+                for (size_t c = first; c < ppos.size() / 9; ++c) { sub_start.push_back(ppos[c * 9 + 1 + 2 * w]); sub_meta.push_back(pn * 4 + w); }
+            if (gpos[3] != gbase) return ge::fail(GE_ERR_STATE, "internal: panel %d covers %lld of its positions", pn, (long long)(gpos[3] - gbase));
+        }
+        sub_start.push_back((int32_t)nP);
+        if (gbase != nP) return ge::fail(GE_ERR_STATE, "internal: panel counts cover %lld of %lld nonzeros", (long long)gbase, (long long)nP);
+    }
+    out->n_pchunks = (int64_t)ppos.size() / 9;
+    if (n_panels > 0) {
+        // Workgroups that start in the panel loop: the panels' share of the epoch's time (see PANEL_STEP_COST), unless the caller
+        // names the number.
+        int32_t pb = rq.panel_blocks;
+        const double w_panels = PANEL_STEP_COST * (double)(panel_steps + 3 * out->n_pchunks), w_main = (double)(N - nP) / 4.0;
+        if (clk.on) std::fprintf(stderr, "[ge_glove_create]   layout: panel steps %lld, chunks %lld, main nonzeros %lld\n", (long long)panel_steps, (long long)out->n_pchunks, (long long)(N - nP));
+        if (pb <= 0) pb = (int32_t)std::lround(w_panels / std::max(w_panels + w_main, 1.0) * (double)rq.blocks);
+        out->panel_blocks = std::max(1, std::min(pb, std::max(rq.blocks, 1)));
+        // The staleness rule with the K of a panel: every block inside the panel holds all its columns, and of the blocks in the
+        // panel loop the panel's share of the panel chunks are inside it.
+        for (int32_t pn = 0; pn < n_panels; ++pn) {
+            const double K = std::max(1.0, (double)out->panel_blocks * (double)panel_chunks[(size_t)pn] / (double)std::max<int64_t>(out->n_pchunks, 1));
+            const int32_t m = rq.flush_every > 0 ? std::min<int32_t>(rq.flush_every, LAYOUT_CHUNK)
+                                                 : (int32_t)std::min<double>(LAYOUT_CHUNK, std::max<double>(4.0, std::floor(rq.stale_budget / K)));
+            for (int k = 0; k < 16; ++k) tlim[(size_t)pn * 16 + k] = m;
+            out->flush_min = std::min(out->flush_min, m);
+        }
+    }
     // T: per group the focus rows in ascending order, packed whole; a chunk closes where the next row would overflow it.
     // Runs: the worker loads every column of the group once per chunk (counted here); a column is published and re-read when
     // it has taken its limit of updates since it was last read (counted by k_tile_cuts once the chunks are placed).
     {
-        int64_t placed = 0;
-        for (int32_t g = 0; g < n_tgroups; ++g) {
+        int64_t placed = nP;
+        for (int32_t g = 4 * n_panels; g < n_tgroups; ++g) {
             int32_t used = 0;
             for (int s = 0; s < G; ++s) if (tcols[(size_t)g * G + s] >= 0) ++used;
             int32_t fill = 0;
@@ -445,7 +531,7 @@ ge_status build_blocked_layout(const LayoutRequest &rq, const int32_t *I, const 
     const int64_t n_chunks = (int64_t)cfill.size();
     std::vector<int32_t> cstart((size_t)n_chunks + 1);
     {
-        int64_t pos = 0;
+        int64_t pos = nP;                               // (the panel chunks lie in front of the chunk table's positions)
         for (int64_t c = 0; c < n_chunks; ++c) { cstart[(size_t)c] = (int32_t)pos; pos += cfill[(size_t)c]; }
         cstart[(size_t)n_chunks] = (int32_t)pos;
         if (pos != N) return ge::fail(GE_ERR_STATE, "internal: chunks cover %lld of %lld nonzeros", (long long)pos, (long long)N);
@@ -487,6 +573,24 @@ ge_status build_blocked_layout(const LayoutRequest &rq, const int32_t *I, const 
                                out->n_tchunks, G, d_cuts);
             e = hipGetLastError();
         }
+        if (e == hipSuccess && n_panels > 0) {
+            int32_t *d_ss = nullptr, *d_sm = nullptr;
+            e = tmp.alloc(&d_ss, sub_start.size());
+            if (e == hipSuccess) e = tmp.alloc(&d_sm, sub_meta.size());
+            if (e == hipSuccess) e = hipMalloc((void **)&out->prow0, sizeof(int32_t) * prow0.size());
+            if (e == hipSuccess) e = hipMalloc((void **)&out->prows, sizeof(int32_t) * std::max<size_t>(prows.size(), 1));
+            if (e == hipSuccess) e = hipMalloc((void **)&out->ppos, sizeof(int32_t) * std::max<size_t>(ppos.size(), 1));
+            if (e == hipSuccess) e = hipMemcpyAsync(d_ss, sub_start.data(), sizeof(int32_t) * sub_start.size(), hipMemcpyHostToDevice, stream);
+            if (e == hipSuccess && !sub_meta.empty()) e = hipMemcpyAsync(d_sm, sub_meta.data(), sizeof(int32_t) * sub_meta.size(), hipMemcpyHostToDevice, stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(out->prow0, prow0.data(), sizeof(int32_t) * prow0.size(), hipMemcpyHostToDevice, stream);
+            if (e == hipSuccess && !prows.empty()) e = hipMemcpyAsync(out->prows, prows.data(), sizeof(int32_t) * prows.size(), hipMemcpyHostToDevice, stream);
+            if (e == hipSuccess && !ppos.empty()) e = hipMemcpyAsync(out->ppos, ppos.data(), sizeof(int32_t) * ppos.size(), hipMemcpyHostToDevice, stream);
+            if (e == hipSuccess && !sub_meta.empty()) {      // the cuts of the panel chunks: the same count over their (chunk, group) ranges
+                hipLaunchKernelGGL(k_tile_cuts, dim3(grid_for((int64_t)sub_meta.size())), dim3(256), 0, stream, out->bB, d_ss, d_sm, out->tlim,
+                                   (int64_t)sub_meta.size(), G, d_cuts);
+                e = hipGetLastError();
+            }
+        }
         if (e == hipSuccess) e = hipMemcpyAsync(&cuts, d_cuts, sizeof(cuts), hipMemcpyDeviceToHost, stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
@@ -497,6 +601,7 @@ ge_status build_blocked_layout(const LayoutRequest &rq, const int32_t *I, const 
         return ge::fail(e == hipErrorOutOfMemory ? GE_ERR_OOM : GE_ERR_HIP, "blocked layout build failed: %s", hipGetErrorString(e));
     }
     out->P = N; out->n_chunks = n_chunks;
+    out->host_prow0.swap(prow0); out->host_ppos.swap(ppos);
     return GE_OK;
 }
 

@@ -21,6 +21,7 @@ GE_HOT_AUTO, GE_HOT_NONE, GE_HOT_ALL = 0, 1, 2
 GE_DTYPE_F32, GE_DTYPE_BF16 = 0, 1
 GE_LAYOUT_FIXED_CUTS, GE_LAYOUT_PLAIN_LONG_ROWS, GE_LAYOUT_SEPARATE_TABLES, GE_LAYOUT_PACKED_RECORDS, GE_LAYOUT_FIRST_PLACEMENT = 1, 2, 4, 8, 16
 GE_LAYOUT_HUB_TILES, GE_LAYOUT_NO_HUB_TILES = 32, 64
+GE_LAYOUT_HUB_PANELS, GE_LAYOUT_NO_HUB_PANELS = 128, 256
 (GE_STATE_FOCUS, GE_STATE_CONTEXT, GE_STATE_FBIAS, GE_STATE_CBIAS, GE_STATE_GSQ_FOCUS,
  GE_STATE_GSQ_CONTEXT, GE_STATE_GSQ_FBIAS, GE_STATE_GSQ_CBIAS, GE_STATE_M2_FOCUS, GE_STATE_M2_CONTEXT,
  GE_STATE_M2_FBIAS, GE_STATE_M2_CBIAS) = range(12)
@@ -32,7 +33,7 @@ ALL_STATE_NAMES = STATE_NAMES + M2_NAMES
 SYMBOLS = (
     "ge_glove_cfg_default", "ge_glove_create", "ge_glove_epoch", "ge_glove_extract_f32",
     "ge_glove_extract_f64", "ge_glove_get_state", "ge_glove_set_state", "ge_glove_device_ptr",
-    "ge_glove_epoch_order", "ge_glove_get_perm", "ge_glove_rng_state", "ge_glove_last_kernel_ms", "ge_glove_get_info", "ge_glove_tile_info", "ge_glove_destroy",
+    "ge_glove_epoch_order", "ge_glove_get_perm", "ge_glove_rng_state", "ge_glove_last_kernel_ms", "ge_glove_get_info", "ge_glove_tile_info", "ge_glove_panel_info", "ge_glove_destroy",
     "ge_bca_build", "ge_coo_get", "ge_coo_destroy", "ge_exchange_turn_bf16", "ge_glove_context_layout",
     "ge_local_group_create", "ge_local_group_destroy", "ge_local_group_abort", "ge_rccl_unique_id", "ge_rccl_selftest", "ge_sync_cfg_size", "ge_sync_create", "ge_sync_begin", "ge_sync_finish", "ge_sync_turn", "ge_sync_sync",
     "ge_sync_epoch", "ge_sync_hub_rows", "ge_sync_hub_exchange", "ge_sync_hub_exchange_live", "ge_sync_live_rows", "ge_sync_hub_plan", "ge_sync_replicate", "ge_sync_allreduce_f64", "ge_sync_destroy",
@@ -193,6 +194,7 @@ def lib():
     L.ge_glove_last_kernel_ms.argtypes = [vp, f32p, i32p]
     L.ge_glove_get_info.argtypes = [vp, C.POINTER(GloveInfo)]
     L.ge_glove_tile_info.argtypes = [vp, C.POINTER(C.c_int64)]
+    L.ge_glove_panel_info.argtypes = [vp, C.POINTER(C.c_int64)]
     L.ge_glove_set_arith.argtypes = [vp, C.c_int32]
     L.ge_glove_get_arith.argtypes = [vp, i32p]
     L.ge_glove_destroy.argtypes = [vp]; L.ge_glove_destroy.restype = None

@@ -43,7 +43,7 @@ class Configuration:
       mode: hogwild|deterministic|stratified   strata: <P, 0 = default>   shuffle: java|device|none   seed: <long>   id: <ordinal>
       hot: auto|none|all   workers: <int>   dtype: f32|bf16
       hot_theta, stale_budget, flush_every, blocks_per_cu (ge_glove_cfg; 0 / absent = library default)
-      layout: [fixed_cuts, plain_long_rows, separate_tables, packed_records, first_placement, hub_tiles, no_hub_tiles]   bca_table_slots, bca_pool_entries (ge_bca_cfg sizing)
+      layout: [fixed_cuts, plain_long_rows, separate_tables, packed_records, first_placement, hub_tiles, no_hub_tiles, hub_panels, no_hub_panels]   bca_table_slots, bca_pool_entries (ge_bca_cfg sizing)
     """
 
     def __init__(self, d=None):
@@ -258,7 +258,8 @@ _HOT = {"auto": capi.GE_HOT_AUTO, "none": capi.GE_HOT_NONE, "all": capi.GE_HOT_A
 _SHUFFLES = {"java": capi.GE_SHUFFLE_JAVA, "device": capi.GE_SHUFFLE_DEVICE, "none": capi.GE_SHUFFLE_NONE}
 _LAYOUT = {"default": 0, "fixed_cuts": capi.GE_LAYOUT_FIXED_CUTS, "plain_long_rows": capi.GE_LAYOUT_PLAIN_LONG_ROWS,
            "separate_tables": capi.GE_LAYOUT_SEPARATE_TABLES, "packed_records": capi.GE_LAYOUT_PACKED_RECORDS,
-           "first_placement": capi.GE_LAYOUT_FIRST_PLACEMENT, "hub_tiles": capi.GE_LAYOUT_HUB_TILES, "no_hub_tiles": capi.GE_LAYOUT_NO_HUB_TILES}
+           "first_placement": capi.GE_LAYOUT_FIRST_PLACEMENT, "hub_tiles": capi.GE_LAYOUT_HUB_TILES, "no_hub_tiles": capi.GE_LAYOUT_NO_HUB_TILES,
+           "hub_panels": capi.GE_LAYOUT_HUB_PANELS, "no_hub_panels": capi.GE_LAYOUT_NO_HUB_PANELS}
 
 
 class Adagrad:
@@ -440,6 +441,12 @@ class Adagrad:
         out = (C.c_int64 * 4)()
         capi.check(capi.lib().ge_glove_tile_info(self._h, out))
         return {"tile_chunks": out[0], "tile_nonzeros": out[1], "group": out[2], "tile_columns": out[3]}
+
+    def panel_info(self):
+        """The hub panels of the handle's layout (ge_glove_panel_info): all zero for a handle without panels."""
+        out = (C.c_int64 * 4)()
+        capi.check(capi.lib().ge_glove_panel_info(self._h, out))
+        return {"panel_chunks": out[0], "panel_nonzeros": out[1], "panel_columns": out[2], "panel_blocks": out[3]}
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:

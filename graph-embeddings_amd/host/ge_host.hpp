@@ -425,6 +425,8 @@ struct Configuration {
                             else if (nm == "first_placement") c.device.layout_flags |= GE_LAYOUT_FIRST_PLACEMENT;
                             else if (nm == "hub_tiles") c.device.layout_flags |= GE_LAYOUT_HUB_TILES;
                             else if (nm == "no_hub_tiles") c.device.layout_flags |= GE_LAYOUT_NO_HUB_TILES;
+                            else if (nm == "hub_panels") c.device.layout_flags |= GE_LAYOUT_HUB_PANELS;
+                            else if (nm == "no_hub_panels") c.device.layout_flags |= GE_LAYOUT_NO_HUB_PANELS;
                             else if (!nm.empty() && nm != "default") throw std::invalid_argument("device.layout: unknown flag " + nm);
                         }
                     }

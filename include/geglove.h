@@ -232,9 +232,16 @@ typedef struct {
  *                count >= rows / 8, on fp32 AdaGrad handles with dim % 4 == 0, dim <= 252, that own every focus row and hold
  *                >= 2^25 nonzeros; every other handle keeps its chunk table and its kernel.  Ignored where the handle's kernel
  *                has no tile walk (bf16 rows, Adam / AMSGrad, other dims, shards).
- * NO_HUB_TILES   never build hub tiles (wins over HUB_TILES). */
+ * NO_HUB_TILES   never build hub tiles (wins over HUB_TILES).
+ * HUB_PANELS     hub panels: four consecutive full groups of tile columns form a panel; the four wavefronts of a
+ *                workgroup hold one group each and pass every focus row of a panel chunk from one to the next, so the row streams
+ *                once per 16 columns; groups that fill no panel stay tiles.  Default: handles that build hub tiles by default (>= 2^25
+ *                nonzeros).  Under this flag a smaller handle builds its panels from forced tiles, as under HUB_TILES (tests, small
+ *                matrices).
+ * NO_HUB_PANELS  never build hub panels (wins over HUB_PANELS): the handle's layout, kernel and results are those of a library
+ *                without panels. */
 enum { GE_LAYOUT_FIXED_CUTS = 1, GE_LAYOUT_PLAIN_LONG_ROWS = 2, GE_LAYOUT_SEPARATE_TABLES = 4, GE_LAYOUT_PACKED_RECORDS = 8, GE_LAYOUT_FIRST_PLACEMENT = 16,
-       GE_LAYOUT_HUB_TILES = 32, GE_LAYOUT_NO_HUB_TILES = 64 };
+       GE_LAYOUT_HUB_TILES = 32, GE_LAYOUT_NO_HUB_TILES = 64, GE_LAYOUT_HUB_PANELS = 128, GE_LAYOUT_NO_HUB_PANELS = 256 };
 
 /* What the library decided for a handle (reporting / DESIGN.md numbers). */
 typedef struct {
@@ -320,6 +327,11 @@ ge_status ge_glove_get_info(ge_glove *h, ge_glove_info *info);
 /* The hub tiles of a handle's layout (GE_LAYOUT_HUB_TILES): out = [tile chunks, nonzeros inside them, columns per group, columns in
  * tiles]; all zero for a handle without tiles.  ge_glove_info.chunks includes the tile chunks, hub_chunks stays the column-major ones. */
 ge_status ge_glove_tile_info(ge_glove *h, int64_t out[4]);
+
+/* The hub panels of a handle's layout (GE_LAYOUT_HUB_PANELS): out = [panel chunks, nonzeros inside them, columns in panels, workgroups
+ * that start in the panel loop]; all zero for a handle without panels.  The panel chunks have a queue of their own: they are no part
+ * of ge_glove_info.chunks, and ge_glove_tile_info counts only what stayed tiles.  ge_glove_epoch_order lists them first. */
+ge_status ge_glove_panel_info(ge_glove *h, int64_t out[4]);
 
 /* GE_MODE_STRATIFIED handles: choose the arithmetic of the following epochs (GE_ARITH_*; JAVA after create).  A NULL handle or an
  * unknown value is GE_ERR_ARG, a handle of another mode GE_ERR_STATE, GE_ARITH_FP32 with a dim that has no lane shape GE_ERR_ARG.

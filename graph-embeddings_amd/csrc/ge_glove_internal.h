@@ -44,6 +44,7 @@ struct EvalView {
     double xmax;
     int32_t vocab_size, dim, row_begin, row_end, cost_kind, emb16, device;
     hipStream_t stream;
+    float learning_rate;                 // cfg.learning_rate (fold.hip: the default step of a fold-in)
 };
 ge_status glove_eval_view(const ge_glove *h, EvalView *out);
 

@@ -2250,6 +2250,7 @@ ge_status glove_eval_view(const ge_glove *h, EvalView *out) {
     out->xmax = h->cfg.xmax; out->vocab_size = h->cfg.vocab_size; out->dim = h->cfg.dim;
     out->row_begin = h->cfg.row_begin; out->row_end = h->cfg.row_begin + h->rows;
     out->cost_kind = h->cfg.cost; out->device = h->cfg.device; out->stream = h->stream;
+    out->learning_rate = h->cfg.learning_rate;
     return GE_OK;
 }
 ge_status glove_sync_view(ge_glove *h, int32_t *opt, int32_t *mode, void **stream, int32_t *device) {

@@ -49,7 +49,12 @@ SYMBOLS = (
     "ge_kmeans_cfg_default", "ge_kmeans_cfg_size", "ge_kmeans_create", "ge_glove_kmeans_create", "ge_kmeans_set_centroids", "ge_kmeans_step",
     "ge_kmeans_run", "ge_kmeans_get", "ge_kmeans_last_kernel_ms", "ge_kmeans_destroy",
     "ge_glove_predict_create", "ge_glove_predict_run", "ge_predict_last_kernel_ms", "ge_predict_get", "ge_predict_destroy",
+    "ge_fold_cfg_default", "ge_fold_cfg_size", "ge_glove_fold_create", "ge_glove_fold_run", "ge_fold_last_kernel_ms", "ge_fold_get",
+    "ge_fold_destroy", "ge_foldin_mask",
 )
+GE_FOLD_FOCUS, GE_FOLD_CONTEXT = 0, 1
+FOLD_SIDES = {"focus": GE_FOLD_FOCUS, "context": GE_FOLD_CONTEXT}
+FOLD_SHUFFLES = {"none": GE_SHUFFLE_NONE, "device": GE_SHUFFLE_DEVICE, "java": GE_SHUFFLE_JAVA}
 GE_NN_COSINE, GE_NN_DOT = 0, 1
 NN_METRICS = {"cosine": GE_NN_COSINE, "dot": GE_NN_DOT}
 GE_KM_COSINE, GE_KM_EUCLID = 0, 1
@@ -139,6 +144,10 @@ class SynthCfg(C.Structure):
 class RankSummary(C.Structure):
     _fields_ = [("n", C.c_int64), ("mrr", C.c_double), ("mean_rank", C.c_double), ("hits1", C.c_int64), ("hits10", C.c_int64),
                 ("hits100", C.c_int64)]
+
+
+class FoldCfg(C.Structure):
+    _fields_ = [("side", C.c_int32), ("epochs", C.c_int32), ("shuffle", C.c_int32), ("learning_rate", C.c_float), ("seed", C.c_int64)]
 
 
 class GeError(RuntimeError):
@@ -257,6 +266,7 @@ def lib():
     _declare_rank(L)
     _declare_kmeans(L)
     _declare_predict(L)
+    _declare_fold(L)
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int:      # default restype -> ge_status
@@ -765,6 +775,104 @@ class Prediction:
             self.close()
         except Exception:
             pass
+
+
+def _declare_fold(L):
+    """The fold-in section of include/geglove.h."""
+    vp, i32p, i64p, f32p, f64p = C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_double)
+    L.ge_fold_cfg_default.argtypes = [C.POINTER(FoldCfg)]; L.ge_fold_cfg_default.restype = None
+    L.ge_fold_cfg_size.argtypes = []; L.ge_fold_cfg_size.restype = C.c_int32
+    if L.ge_fold_cfg_size() != C.sizeof(FoldCfg):
+        raise ImportError("libgeglove.so was built from another revision of include/geglove.h (ge_fold_cfg is %d bytes there, %d here): "
+                          "rebuild with `make -C graph-embeddings_amd/csrc`" % (L.ge_fold_cfg_size(), C.sizeof(FoldCfg)))
+    L.ge_glove_fold_create.argtypes = [vp, i64p, i32p, f32p, C.c_int64, C.POINTER(FoldCfg), C.POINTER(vp)]
+    L.ge_glove_fold_run.argtypes = [vp, f32p, f32p, f32p, f32p, f32p, f64p]
+    L.ge_fold_last_kernel_ms.argtypes = [vp, f32p]
+    L.ge_fold_get.argtypes = [vp, i64p, i64p, i32p, i64p]
+    L.ge_fold_destroy.argtypes = [vp]; L.ge_fold_destroy.restype = None
+    L.ge_foldin_mask.argtypes = [C.c_uint64, C.c_int64, C.c_double, C.POINTER(C.c_uint8)]
+
+
+class Folding:
+    """A ge_fold set on a trainer handle: Folding(glove_handle, row_ptr, idx, X, side, epochs, shuffle, lr, seed), then run() after
+    any epoch.  Row r holds the entries [row_ptr[r], row_ptr[r + 1]) of (idx, X): ids of the frozen side (columns for side "focus",
+    focus rows for side "context").  lr 0 = the handle's.  Close it before the trainer handle goes."""
+
+    def __init__(self, glove_handle, row_ptr, idx, X, side="focus", epochs=10, shuffle="device", lr=0.0, seed=0):
+        import numpy as np
+        row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
+        idx = np.ascontiguousarray(idx, dtype=np.int32); X = np.ascontiguousarray(X, dtype=np.float32)
+        if row_ptr.ndim != 1 or row_ptr.shape[0] < 1 or not (idx.shape == X.shape and idx.ndim == 1):
+            raise ValueError("row_ptr must hold n_rows + 1 offsets; idx, X must be one-dimensional arrays of one length")
+        if int(row_ptr[-1]) != idx.shape[0]:
+            raise ValueError("the last offset of row_ptr must be the length of idx")
+        cfg = FoldCfg()
+        lib().ge_fold_cfg_default(C.byref(cfg))
+        cfg.side = FOLD_SIDES[side] if isinstance(side, str) else int(side)
+        cfg.shuffle = FOLD_SHUFFLES[shuffle] if isinstance(shuffle, str) else int(shuffle)
+        cfg.epochs, cfg.learning_rate, cfg.seed = int(epochs), float(lr), int(seed)
+        # an array of length 0 has no address worth passing: the library only requires the pointers to be non-null
+        pad = lambda a: a if a.shape[0] else np.zeros(1, a.dtype)
+        h = C.c_void_p()
+        check(lib().ge_glove_fold_create(glove_handle, row_ptr.ctypes.data_as(C.POINTER(C.c_int64)), pad(idx).ctypes.data_as(C.POINTER(C.c_int32)),
+                                         pad(X).ctypes.data_as(C.POINTER(C.c_float)), row_ptr.shape[0] - 1, C.byref(cfg), C.byref(h)))
+        self._h = h
+        self.n_rows, self.epochs = row_ptr.shape[0] - 1, int(epochs)
+        self.dim = self.info["dim"]
+
+    def run(self, init_rows=None, init_bias=None):
+        """(rows float32[n_rows, dim], bias float32[n_rows], cost float32[n_rows, E], history float64[E])."""
+        import numpy as np
+        f32p = C.POINTER(C.c_float)
+        ir = ib = None
+        if init_rows is not None:
+            ir = np.ascontiguousarray(init_rows, dtype=np.float32)
+            if ir.shape != (self.n_rows, self.dim):
+                raise ValueError("init_rows must be [n_rows, dim]")
+        if init_bias is not None:
+            ib = np.ascontiguousarray(init_bias, dtype=np.float32)
+            if ib.shape != (self.n_rows,):
+                raise ValueError("init_bias must be [n_rows]")
+        rows = np.empty((self.n_rows, self.dim), dtype=np.float32)
+        bias = np.empty(self.n_rows, dtype=np.float32)
+        cost = np.empty((self.n_rows, self.epochs), dtype=np.float32)
+        history = np.empty(self.epochs, dtype=np.float64)
+        check(lib().ge_glove_fold_run(self._h, None if ir is None else ir.ctypes.data_as(f32p), None if ib is None else ib.ctypes.data_as(f32p),
+                                      rows.ctypes.data_as(f32p), bias.ctypes.data_as(f32p), cost.ctypes.data_as(f32p),
+                                      history.ctypes.data_as(C.POINTER(C.c_double))))
+        return rows, bias, cost, history
+
+    @property
+    def kernel_ms(self):
+        ms = C.c_float()
+        check(lib().ge_fold_last_kernel_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    @property
+    def info(self):
+        """{n_rows, nnz, dim, path}: path = E * the longest row, the sequential updates that bound a run from below."""
+        n, z, d, p = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int64()
+        check(lib().ge_fold_get(self._h, C.byref(n), C.byref(z), C.byref(d), C.byref(p)))
+        return {"n_rows": n.value, "nnz": z.value, "dim": d.value, "path": p.value}
+
+    def close(self):
+        if self._h:
+            lib().ge_fold_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def foldin_mask(seed, n, fraction):
+    """ge_foldin_mask: uint8[n], 1 where vertex v is late (a function of seed, v and fraction alone; no device)."""
+    import numpy as np
+    mask = np.empty(n, dtype=np.uint8)
+    check(lib().ge_foldin_mask(int(seed) & 0xFFFFFFFFFFFFFFFF, n, float(fraction), mask.ctypes.data_as(C.POINTER(C.c_uint8))))
+    return mask
 
 
 def _declare_kmeans(L):

@@ -275,7 +275,11 @@ struct Configuration {
              long long clusters = 0; std::string clusters_metric = "cosine"; long long clusters_iterations = 50;
              // K > 0: after the last epoch list the K best missing links of every kept vertex among the kept vertices, the row's known
              // nonzeros and the vertex itself left out (ge_glove_predict_*), and write <name>.links.tsv; -1 = a value that is no integer >= 0
-             long long predict = 0; } device;
+             long long predict = 0;
+             // F > 0: the vertices ge_foldin_mask(seed, V, F) names are late -- their rows are withheld from training and folded in
+             // after the last epoch (ge_glove_fold_*, `foldin_epochs` epochs on the focus side), <name>.foldin.tsv lists them;
+             // late / vertices: the split's counts once the matrix is known (the banner shows them)
+             double foldin = 0; long long foldin_epochs = 50, foldin_late = -1, foldin_vertices = -1; } device;
     std::vector<std::string> ignored_keys;     // legacy keys of the shipped YAMLs that the bean does not know
 
     int getThreads() const {       // Configuration.java:71-73
@@ -291,6 +295,14 @@ struct Configuration {
     bool ranking() const { return device.rank > 0; }
     bool clustering() const { return device.clusters > 0; }
     bool predicting() const { return device.predict > 0; }
+    bool foldingIn() const { return device.foldin > 0; }
+    // the whole scalar as a number, else NaN (which fails every range check)
+    static double whole_fraction(const YNode &n) {
+        const std::string &t = n.scalar;
+        char *end = nullptr;
+        const double v = std::strtod(t.c_str(), &end);
+        return (n.kind == YNode::Scalar && !t.empty() && *end == 0) ? v : std::numeric_limits<double>::quiet_NaN();
+    }
     // the whole scalar as an integer >= 0 below 2^31, else -1
     static long long whole_number(const YNode &n) {
         const std::string &t = n.scalar;
@@ -385,12 +397,7 @@ struct Configuration {
                     else if (q.first == "pca") c.device.pca = q.second.scalar;
                     else if (q.first == "neighbors") c.device.neighbors = (int)num(&q.second);
                     else if (q.first == "neighbors_metric") c.device.neighbors_metric = q.second.scalar;
-                    else if (q.first == "holdout") {                                            // a number, all of it: anything else fails the check
-                        const std::string &t = q.second.scalar;
-                        char *end = nullptr;
-                        const double v = std::strtod(t.c_str(), &end);
-                        c.device.holdout = (q.second.kind == YNode::Scalar && !t.empty() && *end == 0) ? v : std::numeric_limits<double>::quiet_NaN();
-                    }
+                    else if (q.first == "holdout") c.device.holdout = whole_fraction(q.second);     // a number, all of it: anything else fails the check
                     else if (q.first == "rank") {                                               // an integer >= 0, all of it
                         const std::string &t = q.second.scalar;
                         char *end = nullptr;
@@ -403,6 +410,8 @@ struct Configuration {
                     else if (q.first == "clusters_metric") c.device.clusters_metric = q.second.scalar;
                     else if (q.first == "clusters_iterations") c.device.clusters_iterations = whole_number(q.second);
                     else if (q.first == "predict") c.device.predict = whole_number(q.second);
+                    else if (q.first == "foldin") c.device.foldin = whole_fraction(q.second);
+                    else if (q.first == "foldin_epochs") c.device.foldin_epochs = whole_number(q.second);
                     else if (q.first == "exchange") c.device.exchange = q.second.scalar;        // overlap | sync
                     else if (q.first == "transport") c.device.transport = q.second.scalar;      // auto | rccl | host
                     else if (q.first == "wire") c.device.wire = q.second.scalar;                // bf16 | f32
@@ -465,6 +474,10 @@ struct Configuration {
         if (c.device.predict < 0 || c.device.predict > 128)
             throw InvalidConfigurationException("Invalid device.predict, choose a number of links to predict per vertex from 1 to 128 (0 = off)");
         if (c.predicting() && c.device.gpus > 1) throw InvalidConfigurationException("device.predict runs on one rank only, set device.gpus: 1");
+        if (!(c.device.foldin >= 0 && c.device.foldin <= 0.5)) throw InvalidConfigurationException("Invalid device.foldin, choose a fraction from 0 to 0.5 (0 = off)");
+        if (c.device.foldin_epochs < 1 || c.device.foldin_epochs > 1024) throw InvalidConfigurationException("Invalid device.foldin_epochs, choose a number from 1 to 1024");
+        if (c.foldingIn() && c.holdingOut()) throw InvalidConfigurationException("device.foldin and device.holdout split the matrix differently, set one of them");
+        if (c.foldingIn() && c.device.gpus > 1) throw InvalidConfigurationException("device.foldin runs on one rank only, set device.gpus: 1");
     }
 
     static std::string similarity_to_string(const std::map<std::string, std::string> &m) {     // SimilarityGroup.toString
@@ -513,6 +526,9 @@ struct Configuration {
         if (clustering()) L.push_back("Clusters: " + std::to_string(device.clusters) + " (" + device.clusters_metric + ", at most " +
                                       std::to_string(device.clusters_iterations) + " iterations)");
         if (predicting()) L.push_back("Predict: the " + std::to_string(device.predict) + " best missing links of every kept vertex, known nonzeros filtered");
+        if (foldingIn()) L.push_back("Foldin: " + java_number(device.foldin, false) + ", " + std::to_string(device.foldin_epochs) + " epochs" +
+                                     (device.foldin_vertices < 0 ? std::string() : " (" + std::to_string(device.foldin_late) + " of " +
+                                                                                    std::to_string(device.foldin_vertices) + " vertices late)"));
         return L;
     }
 };
@@ -1058,6 +1074,60 @@ private:
     std::vector<float> X_, hX_;
 };
 
+// `device: { foldin: F }`: the matrix the trainer sees -- every nonzero whose row vertex ge_foldin_mask(seed, V, F) does not name, in
+// matrix order, with the FULL matrix's max() and the unchanged vocabulary (a late vertex keeps its column, so its context row
+// trains as always) -- and the withheld rows beside it as the set of ge_glove_fold_create: late vertices ascending, each row's
+// entries in matrix order.
+class FoldinMatrix : public CoOccurrenceMatrix {
+public:
+    FoldinMatrix(const CoOccurrenceMatrix &full, uint64_t seed, double fraction) : full_(full) {
+        const int64_t N = full.coOccurrenceCount();
+        const int V = full.vocabSize();
+        std::vector<uint8_t> mask((size_t)V);
+        check(ge_foldin_mask(seed, V, fraction, mask.data()));
+        std::vector<int32_t> place((size_t)V, -1);
+        for (int v = 0; v < V; ++v) if (mask[(size_t)v]) { place[(size_t)v] = (int32_t)late_.size(); late_.push_back(v); }
+        const int32_t *I = full.dataI(), *J = full.dataJ(); const float *X = full.dataX();
+        ptr_.assign(late_.size() + 1, 0);
+        for (int64_t k = 0; k < N; ++k) {
+            if (place[(size_t)I[k]] >= 0) ++ptr_[(size_t)place[(size_t)I[k]] + 1];
+            else { I_.push_back(I[k]); J_.push_back(J[k]); X_.push_back(X[k]); }
+        }
+        for (size_t r = 0; r < late_.size(); ++r) ptr_[r + 1] += ptr_[r];
+        lateIdx_.resize((size_t)ptr_.back()); lateX_.resize((size_t)ptr_.back());
+        std::vector<int64_t> at(ptr_.begin(), ptr_.end() - 1);
+        for (int64_t k = 0; k < N; ++k) {
+            const int32_t r = place[(size_t)I[k]];
+            if (r >= 0) { lateIdx_[(size_t)at[(size_t)r]] = J[k]; lateX_[(size_t)at[(size_t)r]++] = X[k]; }
+        }
+        const std::string of = " of the " + std::to_string(V) + " vertices";
+        if (I_.empty()) throw std::runtime_error("device.foldin: " + java_number(fraction, false) + " leaves no nonzero to train on");
+        if (late_.empty()) throw std::runtime_error("device.foldin: " + java_number(fraction, false) + " names none" + of + ", nothing to fold in");
+        if (lateIdx_.empty()) { lateIdx_.push_back(0); lateX_.push_back(0.0f); }     // never a null pointer beside the offsets
+    }
+    int vocabSize() const override { return full_.vocabSize(); }
+    double max() const override { return full_.max(); }
+    std::string getKey(int index) const override { return full_.getKey(index); }
+    int8_t getType(int index) const override { return full_.getType(index); }
+    int cIdx_I(int i) const override { return I_[(size_t)i]; }
+    int cIdx_J(int j) const override { return J_[(size_t)j]; }
+    float cIdx_C(int i) const override { return X_[(size_t)i]; }
+    int coOccurrenceCount() const override { return (int)I_.size(); }
+    void shuffle() override {}
+    const int32_t *dataI() const override { return I_.data(); }
+    const int32_t *dataJ() const override { return J_.data(); }
+    const float *dataX() const override { return X_.data(); }
+    const std::vector<int32_t> &lateVertices() const { return late_; }
+    const std::vector<int64_t> &latePtr() const { return ptr_; }
+    const std::vector<int32_t> &lateIdx() const { return lateIdx_; }
+    const std::vector<float> &lateX() const { return lateX_; }
+private:
+    const CoOccurrenceMatrix &full_;
+    std::vector<int32_t> I_, J_, late_, lateIdx_;
+    std::vector<int64_t> ptr_;
+    std::vector<float> X_, lateX_;
+};
+
 // ------------------------------------------------------------------------------------------------
 // Optimizer
 // ------------------------------------------------------------------------------------------------
@@ -1075,6 +1145,10 @@ struct Optimum {                                 // J/opt/Optimum.java
     int32_t predictK = 0;
     std::vector<int32_t> predictRows, predictIndex, predictCount;
     std::vector<float> predictScore;
+    // `device.foldin`: the late vertices ascending, their nonzero counts, and the cost of their first and last fold-in epoch
+    std::vector<int32_t> foldinRows;
+    std::vector<int64_t> foldinNonzeros;
+    std::vector<float> foldinFirstCost, foldinLastCost;
 };
 struct IOptimizer {                              // J/opt/IOptimizer.java:6-11
     virtual ~IOptimizer() = default;
@@ -1094,6 +1168,12 @@ struct IOptimizer {                              // J/opt/IOptimizer.java:6-11
     // itself left out, lists as in include/geglove.h
     virtual void predict(const std::vector<int32_t> &, const std::vector<int64_t> &, const std::vector<int32_t> &, const std::vector<int32_t> &, int32_t, Optimum &) {
         throw std::invalid_argument("this optimizer predicts no links");
+    }
+    // `device.foldin`: fit the focus rows of the late vertices `rows` from their withheld nonzeros (the set of ge_glove_fold_create)
+    // against the trained context side, from zero, patch them and their fBias into the trained tables and extract the result again
+    virtual void foldIn(const std::vector<int32_t> &, const std::vector<int64_t> &, const std::vector<int32_t> &, const std::vector<float> &, int32_t, int64_t,
+                        Optimum &) {
+        throw std::invalid_argument("this optimizer folds no late vertices in");
     }
 };
 enum class CostFunction { GLOVE, PGLOVE };       // GloveCost / PGloveCost
@@ -1190,6 +1270,34 @@ public:
         opt.predictIndex.resize(I.size() * (size_t)K); opt.predictScore.resize(I.size() * (size_t)K); opt.predictCount.resize(I.size());
         check(ge_glove_predict_run(p, K, opt.predictIndex.data(), opt.predictScore.data(), opt.predictCount.data()));
     }
+    void foldIn(const std::vector<int32_t> &rows, const std::vector<int64_t> &ptr, const std::vector<int32_t> &idx, const std::vector<float> &X, int32_t epochs,
+                int64_t seed, Optimum &opt) override {
+        if (ge_fold_cfg_size() != (int32_t)sizeof(ge_fold_cfg))
+            throw std::runtime_error("libgeglove.so and this host were built from different revisions of include/geglove.h; rebuild both");
+        ge_fold_cfg cfg;
+        ge_fold_cfg_default(&cfg);
+        cfg.side = GE_FOLD_FOCUS; cfg.epochs = epochs; cfg.seed = seed;
+        ge_fold *f = nullptr;
+        check(ge_glove_fold_create(h_.get(), ptr.data(), idx.data(), X.data(), (int64_t)rows.size(), &cfg, &f));
+        std::unique_ptr<ge_fold, DelFold> set(f);
+        const size_t n = rows.size(), D = (size_t)dim_, E = (size_t)epochs;
+        std::vector<float> folded(n * D), bias(n), cost(n * E);
+        check(ge_glove_fold_run(f, nullptr, nullptr, folded.data(), bias.data(), cost.data(), nullptr));
+        // the late vertices' focus rows and fBias take their fitted values; every other entry goes back as it came
+        std::vector<float> focus((size_t)vocab_ * D), fbias((size_t)vocab_);
+        check(ge_glove_get_state(h_.get(), GE_STATE_FOCUS, focus.data(), (int64_t)focus.size()));
+        check(ge_glove_get_state(h_.get(), GE_STATE_FBIAS, fbias.data(), (int64_t)fbias.size()));
+        for (size_t r = 0; r < n; ++r) {
+            std::copy(folded.begin() + (std::ptrdiff_t)(r * D), folded.begin() + (std::ptrdiff_t)((r + 1) * D), focus.begin() + (std::ptrdiff_t)((size_t)rows[r] * D));
+            fbias[(size_t)rows[r]] = bias[r];
+        }
+        check(ge_glove_set_state(h_.get(), GE_STATE_FOCUS, focus.data(), (int64_t)focus.size()));
+        check(ge_glove_set_state(h_.get(), GE_STATE_FBIAS, fbias.data(), (int64_t)fbias.size()));
+        opt.foldinRows = rows;
+        opt.foldinNonzeros.resize(n); opt.foldinFirstCost.resize(n); opt.foldinLastCost.resize(n);
+        for (size_t r = 0; r < n; ++r) { opt.foldinNonzeros[r] = ptr[r + 1] - ptr[r]; opt.foldinFirstCost[r] = cost[r * E]; opt.foldinLastCost[r] = cost[r * E + E - 1]; }
+        opt.result = extractResult();
+    }
     std::vector<double> extractResult() override {
         std::vector<double> out((size_t)vocab_ * (size_t)dim_);
         check(ge_glove_extract_f64(h_.get(), out.data()));
@@ -1200,6 +1308,7 @@ private:
     struct DelEval { void operator()(ge_eval *e) const { ge_eval_destroy(e); } };
     struct DelRank { void operator()(ge_rank *r) const { ge_rank_destroy(r); } };
     struct DelPredict { void operator()(ge_predict *p) const { ge_predict_destroy(p); } };
+    struct DelFold { void operator()(ge_fold *f) const { ge_fold_destroy(f); } };
     std::unique_ptr<ge_glove, Del> h_;
     std::unique_ptr<ge_eval, DelEval> eval_;      // declared after h_: destroyed before the handle it reads
     int64_t nHeld_ = 0;
@@ -1540,6 +1649,26 @@ inline std::string writeHoldout(const Configuration &config, const Optimum &opti
         out << b;
     }
     return "wrote " + std::to_string(optimum.holdoutHistory.size()) + " epochs to " + outputFolder + "/" + file;
+}
+
+// `device: { foldin: F }`: <fileName>.foldin.tsv carries the banner, then one line per late vertex in ascending id: the id, its key,
+// the nonzeros of its withheld row, and the cost of its first and of its last fold-in epoch (%.9g: text that parses back to the same float).
+inline std::string writeFoldin(const Configuration &config, const Optimum &optimum, const CoOccurrenceMatrix &m, const std::string &fileName,
+                               const std::string &outputFolder) {
+    std::filesystem::create_directories(outputFolder);
+    const std::string file = fileName + ".foldin.tsv";
+    std::ofstream out(outputFolder + "/" + file);
+    if (!out) throw std::runtime_error("cannot open " + file + " in " + outputFolder);
+    for (auto &l : config.banner()) out << "# " << l << "\n";
+    char b[96];
+    long long nonzeros = 0;
+    for (size_t r = 0; r < optimum.foldinRows.size(); ++r) {
+        std::snprintf(b, sizeof b, "\t%lld\t%.9g\t%.9g\n", (long long)optimum.foldinNonzeros[r], (double)optimum.foldinFirstCost[r], (double)optimum.foldinLastCost[r]);
+        out << optimum.foldinRows[r] << "\t" << m.getKey(optimum.foldinRows[r]) << b;
+        nonzeros += optimum.foldinNonzeros[r];
+    }
+    return "folded " + std::to_string(optimum.foldinRows.size()) + " late vertices in from " + std::to_string(nonzeros) + " withheld nonzeros; wrote " +
+           outputFolder + "/" + file;
 }
 
 // `device: { rank: Q }`: <fileName>.rank.tsv carries the banner, then the summary line mrr, mean_rank (%.17g), hits1, hits10, hits100, n,

@@ -2,7 +2,7 @@
 // Same single flag, same settings banner, same output files ./out/<name>.{vectors,dict}.tsv
 // (and <name>.neighbors.tsv with `device: { neighbors: K }`, <name>.holdout.tsv with `device: { holdout: F }`,
 // <name>.rank.tsv with `device: { rank: Q }`, <name>.clusters.tsv with `device: { clusters: K }`,
-// <name>.links.tsv with `device: { predict: K }`).
+// <name>.links.tsv with `device: { predict: K }`, <name>.foldin.tsv with `device: { foldin: F }`).
 #include <ctime>
 #include "ge_host.hpp"
 
@@ -80,12 +80,22 @@ static void runProgram(const Configuration &given) {                        // J
         config.device.holdout_held = split->heldCount(); config.device.holdout_total = matrix->coOccurrenceCount();
         log_info("Graph Embeddings", config.banner().back());
     }
-    const CoOccurrenceMatrix &bca = split ? static_cast<const CoOccurrenceMatrix &>(*split) : *matrix;
+    std::unique_ptr<FoldinMatrix> late;
+    if (config.foldingIn()) {
+        config.device.seed = config.runSeed(); config.device.has_seed = true;      // one seed for the split, the trainer and the fold-in's walk
+        late.reset(new FoldinMatrix(*matrix, (uint64_t)config.device.seed, config.device.foldin));
+        config.device.foldin_late = (long long)late->lateVertices().size(); config.device.foldin_vertices = matrix->vocabSize();
+        log_info("Graph Embeddings", config.banner().back());
+    }
+    const CoOccurrenceMatrix &bca = split ? static_cast<const CoOccurrenceMatrix &>(*split) : late ? static_cast<const CoOccurrenceMatrix &>(*late) : *matrix;
     g_tolerance = config.opt.tolerance;
     std::unique_ptr<IOptimizer> optimizer = createOptimizer(config, bca, progress);
     if (split) { optimizer->holdOut(split->heldI(), split->heldJ(), split->heldX(), split->heldCount()); g_optimizer = optimizer.get(); }
     if (!optimizer->scheduleNote().empty()) log_info("Optimizer", optimizer->scheduleNote());
     Optimum optimum = optimizer->optimize();
+    if (late)                                   // the late vertices get their focus rows before anything reads the tables
+        optimizer->foldIn(late->lateVertices(), late->latePtr(), late->lateIdx(), late->lateX(), (int32_t)config.device.foldin_epochs,
+                          (int64_t)config.device.seed, optimum);
     if (split && config.ranking()) {            // on the tables as the last epoch left them
         std::vector<int32_t> rI, rJ, fIdx; std::vector<int64_t> fPtr;
         split->rankSet(config.device.rank, rI, rJ, fPtr, fIdx);
@@ -106,6 +116,7 @@ static void runProgram(const Configuration &given) {                        // J
     const long long n = writer.write(optimum, bca, "out");
     log_info("EmbeddingTextWriter", "wrote " + std::to_string(n) + " vectors to out/" + writer.vectorsFile());
     if (split) log_info("Holdout", writeHoldout(config, optimum, outFileName, "out"));
+    if (late) log_info("Foldin", writeFoldin(config, optimum, bca, outFileName, "out"));
     if (split && config.ranking()) log_info("Rank", writeRank(config, optimum, outFileName, "out"));
     if (config.predicting()) log_info("Predict", writeLinks(config, optimum, bca, outFileName, "out"));
     if (config.writingNeighbors()) {

@@ -767,6 +767,10 @@ void      ge_eval_destroy(ge_eval *e);     /* before the ge_glove it was created
  * hi(SM(seed ^ 0x484F4C444F5554, k)) < T, T = floor(fraction * 2^32) computed in fp64 (SM, hi: the notation of the synthetic
  * matrix above).  A function of (seed, k, fraction) alone.  fraction outside (0, 0.5] (NaN included): GE_ERR_ARG. */
 ge_status ge_holdout_mask(uint64_t seed, int64_t n, double fraction, uint8_t *mask);
+/* The late-vertex rule of the CLI's fold-in split (see "Fold-in"), HOST ONLY: mask[v] = 1 when vertex v is late, i.e. when
+ * hi(SM(seed ^ 0x464F4C44494E, v)) < T, T = floor(fraction * 2^32) computed in fp64.  A function of (seed, v, fraction) alone.
+ * fraction outside (0, 0.5] (NaN included): GE_ERR_ARG. */
+ge_status ge_foldin_mask(uint64_t seed, int64_t n, double fraction, uint8_t *mask);
 
 /* ------------------------------------------------------------------------------------------
  * Ranking: at which place does column J[k] stand among all V columns when they are ordered by the model's own prediction for
@@ -935,6 +939,81 @@ ge_status ge_kmeans_get(const ge_kmeans *p, int64_t *n, int32_t *dim, int32_t *k
  * around the kernels, in milliseconds (0 = none ran); copies are not counted.  Either out pointer may be NULL. */
 ge_status ge_kmeans_last_kernel_ms(const ge_kmeans *p, float *assign_ms, float *update_ms);
 void      ge_kmeans_destroy(ge_kmeans *p);
+
+/* ------------------------------------------------------------------------------------------
+ * Fold-in: a vector for a vertex that arrives after training.  A new row is a list of entries (id, x) against the trained
+ * rows of the other side; it is fitted by the AdaGrad update of GE_ARITH_FP32 with that other side held constant.  The
+ * reference has no counterpart, so these are product semantics.
+ *   set        new row r, r = 0 .. n_rows-1, holds the nonzeros k in [row_ptr[r], row_ptr[r+1]), n_r of them: (idx[k], X[k]).
+ *              Empty rows are legal; repeated ids inside a row are legal.
+ *   frozen     GE_FOLD_FOCUS: the new rows are focus rows, b = context[idx[k]], fb_other = cBias[idx[k]].
+ *   side       GE_FOLD_CONTEXT: the new rows are context rows (columns), b = focus[idx[k]], fb_other = fBias[idx[k]].
+ *              Rows are read in place, where the handle keeps them, by the rules of ge_glove_eval_*: every mode, plain tables,
+ *              records, packed records, a shard's focus rows counted from row_begin, bf16 rows widened exactly; for a bf16
+ *              context row with hub_index[j] >= 0 the fp32 master row is read.  Nothing is staged.
+ *   state      of a new row: a (D = dim floats) and fb from init_rows / init_bias, or zero; Ga = 1 for every element and
+ *              Gfb = 1.  The accumulators start fresh on every run: E epochs in one run are not two runs of E / 2.
+ *   update     for nonzero (b, x), always AdaGrad, whatever the handle trained with.  Every operation is an IEEE fp32 operation,
+ *              rounded to nearest even, unless marked fp64; nothing is contracted beyond the fmas named under GE_ARITH_FP32.
+ *              Lane shape, dot (the per-lane fmaf chain over a and b, then the tree) and the cost terms l (fp64), w with the
+ *              handle's cost kind and xmax: exactly as GE_ARITH_FP32 states them.  Then
+ *                ic = (float) ((double) dot + ((double) (fb + fb_other) - l));   wc = w * ic;
+ *                per element  g = wc * b;   a' = a - (g / sqrtf(Ga)) * lr;   Ga' = Ga + g * g;
+ *                fb' = fb - wc / sqrtf(Gfb);   Gfb' = Gfb + wc * wc;
+ *              with g taken from the values read before the row changes; sqrtf and / correctly rounded.  lr = cfg.learning_rate,
+ *              or the handle's when that is 0.  The lane shape defines the arithmetic, not the access width: where a row's
+ *              start does not allow a vw-wide access the same elements may be read with narrower loads.  (Every layout a
+ *              handle has today starts its rows on a vw-wide boundary, so the library has no narrower path; a table that
+ *              broke the rule would be GE_ERR_STATE at run, never read differently.)  A dim with more than four chunks is
+ *              GE_ERR_ARG.
+ *   order      epochs e = 0 .. E-1.  GE_SHUFFLE_NONE: ascending k inside an epoch.  GE_SHUFFLE_DEVICE: the q-th update of epoch
+ *              e is the row's B(n_r, K(0))(q)-th nonzero, B and K as under GE_MODE_STRATIFIED, K taken with iteration = e and
+ *              cfg.seed.  The key does not depend on r.
+ *   cost       c[r][e], fp32, from 0 per row and epoch:  c = (float) ((double) c + (0.5 * (double) wc) * (double) ic).
+ *              cost_history[e] = the fp64 sum of c[r][e] over ascending r, from 0.0, computed on the host.
+ *   bytes      a row's results (a, fb, c[r][.]) depend only on its own nonzeros, its init, cfg and the frozen tables: not on the
+ *              other rows, its place in the set, the grid or the run.  No atomics.
+ *   pure read  no trainer table is written; neither the RNG state nor the permutation is touched.  A handle that is never
+ *              folded into produces the bytes it produced before.  ge_glove_fold_run may be called after any epoch and reads
+ *              the tables as they are then; it runs on the trainer handle's stream and is blocking.
+ * Limits, checked on the host before any device work (GE_ERR_ARG): 1 <= n_rows < 2^31; row_ptr[0] == 0 and row_ptr
+ * non-decreasing; fewer than 2^31 nonzeros in all; 1 <= E <= 1024 and n_rows * E < 2^31; idx inside the frozen side's rows --
+ * [0, V), or the shard's [row_begin, row_end) for GE_FOLD_CONTEXT; X finite and > 0, and < 1 for pGloVe; learning_rate 0, or
+ * finite and > 0; side and shuffle known values (GE_SHUFFLE_JAVA has no per-row order); no null mandatory argument.  (What
+ * needs no handle -- the null arguments, n_rows, cfg, the shape of row_ptr, ids below 0, X not finite or not positive -- is
+ * refused first, so without a device as well.)  init values must be finite: a non-finite one is GE_ERR_ARG ("non-finite
+ * input") at run.
+ * Device memory: until ge_fold_destroy a set holds 20 bytes per nonzero (idx, l in fp64, w, x; (l, w) are computed once at
+ * creation), 12 bytes per row, and 4 * n_rows * (dim + 1 + E) bytes of results.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct ge_fold ge_fold;
+enum { GE_FOLD_FOCUS = 0, GE_FOLD_CONTEXT = 1 };
+typedef struct {
+    int32_t side;           /* GE_FOLD_FOCUS: new rows (r, idx, x) fitted as focus rows against the frozen context rows + cBias.
+                               GE_FOLD_CONTEXT: new columns (idx, r, x) fitted as context rows against the frozen focus rows + fBias */
+    int32_t epochs;         /* E, 1 .. 1024 */
+    int32_t shuffle;        /* GE_SHUFFLE_NONE or GE_SHUFFLE_DEVICE; GE_SHUFFLE_JAVA is GE_ERR_ARG */
+    float   learning_rate;  /* 0 = the handle's */
+    int64_t seed;           /* keys the DEVICE walk */
+} ge_fold_cfg;
+void      ge_fold_cfg_default(ge_fold_cfg *cfg);   /* focus, 10 epochs, DEVICE, lr 0, seed 0 */
+int32_t   ge_fold_cfg_size(void);
+/* row_ptr: HOST int64[n_rows + 1]; idx, X: HOST [row_ptr[n_rows]].  The set is uploaded once and lives on the device until
+ * ge_fold_destroy. */
+ge_status ge_glove_fold_create(ge_glove *h, const int64_t *row_ptr, const int32_t *idx, const float *X, int64_t n_rows,
+                               const ge_fold_cfg *cfg, ge_fold **out);
+/* init_rows: HOST float[n_rows * dim] or NULL (zeros); init_bias: HOST float[n_rows] or NULL (zeros).
+ * out_rows float[n_rows * dim], out_bias float[n_rows], out_cost float[n_rows * E] (row-major: row r, epoch e); each may be NULL.
+ * cost_history: double[E] or NULL. */
+ge_status ge_glove_fold_run(ge_fold *f, const float *init_rows, const float *init_bias,
+                            float *out_rows, float *out_bias, float *out_cost, double *cost_history);
+/* Device time of the last run's kernel (hipEvents around it; copies not counted), in milliseconds; 0 = none ran. */
+ge_status ge_fold_last_kernel_ms(const ge_fold *f, float *ms);
+/* *n_rows, *nnz, *dim of the set; *path = E * the longest row.  One wavefront fits one row with every epoch inside one launch,
+ * its updates strictly one after another, so the time of a run is bounded below by `path` sequential updates of the longest row
+ * however many rows the set holds.  Any out pointer may be NULL. */
+ge_status ge_fold_get(const ge_fold *f, int64_t *n_rows, int64_t *nnz, int32_t *dim, int64_t *path);
+void      ge_fold_destroy(ge_fold *f);   /* before the ge_glove it was created for */
 
 /* ------------------------------------------------------------------------------------------ */
 const char *ge_last_error(void);     /* message of the calling thread's last failed call */

@@ -10,6 +10,7 @@ import pytest
 import geglove
 from geglove import capi, synth
 from helpers import make_config
+import chain_ref as CH
 import kmeans_ref as R
 import nn_ref
 
@@ -155,6 +156,36 @@ def test_every_row_of_every_step_within_the_bound(gpu, metric, kind, dim):
         assert km.centroids.tobytes() == R.update(XH, label, before, metric).tobytes()
         assert (changed == n) if step == 0 else (0 <= changed < n)
     print("%s %s dim %d: worst |best - t| = %.3f B" % (metric, kind, dim, worst))
+
+
+# ---- chain tier ---------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("dim", [33, 200])
+@pytest.mark.parametrize("metric", [R.COSINE, R.EUCLID])
+def test_labels_and_best_are_the_chain_bit_for_bit(gpu, metric, dim):
+    """General floats, no bound: z = chain(xh, cen) + h with one fp32 add, the chain the header's "fp32 fmaf chain from 0.0f over
+    ascending d" in numpy (tests/chain_ref.py; test_chain_ref.py shows that it differs from any other order of summation in most
+    scores at these dims), h from kmeans_ref.bias.  K = 130 is two centroid tiles; centroid c + 65 is a copy of centroid c, so
+    every row's best is an exact tie that must go to the lower id."""
+    n, K = 300, 130
+    X = nn_ref.random_rows(800 + dim, n, dim)
+    C = nn_ref.random_rows(900 + dim, K, dim)
+    C[:40] = X[:40]                                                       # some centroids are rows
+    C[K // 2:] = C[:K // 2]
+    XH, cen = R.prepare(X, metric), R.prepare(C, metric)
+    Z = CH.chain(XH, cen) + R.bias(cen, metric)[None, :]
+    assert Z.dtype == np.float32 and np.all(np.isfinite(Z))
+    want_label, want_best = R.assign(Z)
+    assert want_label.max() < K // 2 and len(set(want_label.tolist())) > 10
+    km = capi.Clustering.create(X, K, metric=metric, seed=1)
+    km.set_centroids(C)
+    assert km.centroids.tobytes() == cen.tobytes()
+    km.step()
+    label, best = km.labels, km.best
+    bad = np.flatnonzero((label != want_label) | (best.view(np.uint32) != want_best.view(np.uint32)))
+    assert bad.size == 0, "%d of %d rows differ from the model; row %d: got (%d, %r), want (%d, %r)" % (
+        bad.size, n, bad[0], label[bad[0]], best[bad[0]], want_label[bad[0]], want_best[bad[0]])
+    assert label.tobytes() == want_label.tobytes() and best.tobytes() == want_best.tobytes()
 
 
 # ---- whole runs ---------------------------------------------------------------------------------------------------------

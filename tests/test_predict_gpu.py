@@ -5,7 +5,8 @@ into handles with ge_glove_set_state:
      every designed kind, subsets and the query's own column; and a table long enough for candidate ranges of several tiles,
      whose best columns are filtered and met after the thresholds are set;
   B  the same case on every kind of handle: identical bytes;
-  C  every prediction handed to ge_glove_rank_run with the same filter comes back with rank t + 1 and the same score bits;
+  C  every prediction handed to ge_glove_rank_run with the same filter comes back with rank t + 1 and the same score bits; and on
+     generic floats index, score bits and count are those of the header's fmaf chain in numpy (tests/chain_ref.py), no bound;
   D  generic floats inside the bound derived in predict_ref.py, whose undecided share is capped before the device is asked;
   E  a function of the input alone, and a pure read;
   F  a planted answer."""
@@ -17,6 +18,7 @@ import pytest
 import geglove
 from geglove import capi, synth
 from helpers import make_config
+import chain_ref as CH
 import nn_ref as N
 import predict_ref as P
 import rank_ref as R
@@ -262,6 +264,44 @@ def test_every_prediction_has_its_rank_bit_for_bit(gpu, D):
             bad = np.flatnonzero(rank.reshape(n, K) != np.arange(1, K + 1)[None, :])
             assert bad.size == 0, "query %d slot %d has rank %d" % (bad[0] // K, bad[0] % K, rank[bad[0]])
             assert zt.tobytes() == score.tobytes()
+    finally:
+        h.close()
+
+
+@pytest.mark.parametrize("D", [33, 200])
+def test_generic_floats_are_the_chain_bit_for_bit(gpu, D):
+    """C holds the two score tiles and the gather chain to one another, device against device; this holds all three to the header:
+    z = chain(F[I], C) + cBias with one fp32 add, the chain "the fp32 fmaf chain from 0.0f over ascending d" in numpy
+    (tests/chain_ref.py; test_chain_ref.py shows it differs from any other order of summation in most scores at these dims).
+    Index, score bits and count equal the model under the total order, K = 33 and 128, twin columns for exact ties; and every
+    prediction handed to ge_glove_rank_run comes back with rank t + 1 and the MODEL's score bits."""
+    m, n = 150, 100
+    V = 2 * m
+    F, C, fb, cb = P.float_tables(1700 + D, V, D)
+    C[m:] = C[:m]; cb[m:] = cb[:m]
+    I, _ = _pairs(5 * D, n, V)
+    Z = CH.chain(F[I], C) + cb[None, :]
+    assert Z.dtype == np.float32 and np.all(np.isfinite(Z))
+    lists = [np.flatnonzero(synth.splitmix64(1900 + k, V) % np.uint64(4) == 0) for k in range(n)]
+    h = _handle(V, D)
+    try:
+        _set(h, F, C, fb, cb)
+        for filters, own, K in ((None, False, 128), (lists, True, 33), (None, True, 33), (lists, False, 128)):
+            csr = None if filters is None else P.csr(filters)
+            want = P.topk(Z, K, csr, None, I if own else None)
+            assert np.all(want[2] == K) and np.mean((want[1][:, 1:] == want[1][:, :-1]).any(axis=1)) > 0.5
+            got, _ = _predict(h, I, (K,), csr, None, own)
+            _same(got[K], want, (D, K, own, "filtered" if filters else "plain", "chain model"))
+            per_query = [np.union1d(filters[k] if filters is not None else [], [I[k]] if own else []).astype(np.int32) for k in range(n)]
+            ptr, idx = P.csr([per_query[k] for k in range(n) for _ in range(K)])
+            rk = capi.Ranking(h._h, np.repeat(I, K).astype(np.int32), want[0].reshape(-1), ptr, idx)
+            try:
+                rank, zt, _ = rk.run()
+            finally:
+                rk.close()
+            bad = np.flatnonzero(rank.reshape(n, K) != np.arange(1, K + 1)[None, :])
+            assert bad.size == 0, "query %d slot %d has rank %d" % (bad[0] // K, bad[0] % K, rank[bad[0]])
+            assert zt.tobytes() == want[1].tobytes()
     finally:
         h.close()
 

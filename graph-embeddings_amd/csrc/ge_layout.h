@@ -50,6 +50,7 @@ struct LayoutRequest {
     int32_t panels;          // 1: full groups of tile columns are walked as hub panels, four groups to a panel
     int32_t panel_blocks;    // > 0: that many workgroups start in the panel loop; 0: the panels' share of the epoch's time
     int32_t blocks;          // workgroups of the tile kernel's launch (what panel_blocks is a share of)
+    int32_t panel_div;       // > 8: hub columns with count >= rows / panel_div join panels (not under tile_force); else: the tiles' rows / 8
 };
 
 struct BlockedLayout {

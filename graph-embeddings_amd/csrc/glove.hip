@@ -309,15 +309,22 @@ struct PanelLink {
     int32_t n_rows;           // read from LDS by every wave of the block: the same number in all four
     int32_t lag;              // this stage works on row t - lag at step t (its wave in the block)
     float *nextA, *nextB;     // SINK = PAIR_LDS: the two images of the next stage
+    float *ring;              // KD > 1: the KD + 1 images of stage 0's request ring, RING_IMG floats each
 };
-template <int G, int SRC, int SINK>
+constexpr int RING_IMG = 512;             // floats per image of the ring: a row's image and its accumulator row's behind it (IMG_G)
+// KD: how many rows ahead stage 0 of the panel pipeline requests its focus pair.  1: one row ahead into the
+// other of two images, chosen at compile time (every kernel but the ring kernel).  KD > 1: row t + KD is requested at step t into
+// a ring of KD + 1 images, and the image of row t is read behind vmcnt(2 KD).
+template <int G, int SRC, int SINK, int KD = 1>
 __device__ __forceinline__ void tile_chunk(const GloveParams &p, const int32_t c_lo, const int32_t c_len, const int32_t grp,
                                            float *const setA, float *const setB, float *const tr_c, float *const tr_g,
                                            int32_t *const stg, double &cost_acc, const PanelLink &pl, const int lane) {
     constexpr bool PIPE = SRC == PAIR_LDS || SINK == PAIR_LDS;
     // vector-memory instructions behind a focus pair's request when its image is read: the next row's request, and in front of it
     // the two stores that ended the previous row where this stage stores (see walk_row)
-    constexpr int N_AFTER = SINK == PAIR_MEM ? TILE_N_AFTER : TILE_N_AFTER - 2;
+    constexpr int N_AFTER = KD > 1 ? 2 * KD : SINK == PAIR_MEM ? TILE_N_AFTER : TILE_N_AFTER - 2;
+    static_assert(KD == 1 || (KD >= 2 && SRC == PAIR_MEM && SINK == PAIR_LDS), "the request ring is stage 0's: it stores nothing to memory");
+    static_assert(N_AFTER < 64, "vmcnt is a 6-bit counter");
     static_assert(G >= 2 && G <= 8, "two to eight resident columns");
     const int32_t D = p.D, DS = p.DS;
     const uint32_t row_bytes = (uint32_t)p.RW * 4u;
@@ -361,7 +368,17 @@ __device__ __forceinline__ void tile_chunk(const GloveParams &p, const int32_t c
     int32_t n_row = 0;
     if constexpr (!PIPE) n_row = row_at(0);
     else if constexpr (SRC == PAIR_MEM) n_row = rfl(pl.rows[0]);
-    if constexpr (SRC == PAIR_MEM) request(setA, n_row, true);
+    int ring_cur = 0;                                    // KD > 1: the image of the row that is walked next
+    if constexpr (KD == 1) {
+        if constexpr (SRC == PAIR_MEM) request(setA, n_row, true);
+    } else {
+        // rows 0 .. KD - 1 into images 0 .. KD - 1 (a chunk shorter than that: zero-sized resources, the same 2 KD instructions)
+#pragma unroll
+        for (int q = 0; q < KD; ++q) {
+            const bool live = q < pl.n_rows;
+            request(pl.ring + q * RING_IMG, live ? rfl(pl.rows[q]) : 0, live);
+        }
+    }
 
     // ---- the G resident pairs ----
     float4 a[G], ga[G], a0[G], ga0[G];
@@ -494,9 +511,27 @@ __device__ __forceinline__ void tile_chunk(const GloveParams &p, const int32_t c
             nxt = pos;
             while (nxt < c_len && row_at(nxt) == row) ++nxt;
             more = ri + 1 < pl.n_rows;
-            if constexpr (SRC == PAIR_MEM) n_row = more ? rfl(pl.rows[ri + 1]) : 0;
+            if constexpr (SRC == PAIR_MEM && KD == 1) n_row = more ? rfl(pl.rows[ri + 1]) : 0;
         }
         const float *const img = decltype(CUR)::value ? setB : setA;
+        if constexpr (KD > 1) {
+            // Row ri + KD goes into the image that row ri - 1 was read from (ring_cur - 1, cyclically): that read is complete, its
+            // lgkmcnt wait is inside the asm below.  The rows of a panel chunk are distinct, and no request crosses the chunk's end.
+            const bool ahead = ri + KD < pl.n_rows;
+            const int32_t a_row = ahead ? rfl(pl.rows[ri + KD]) : 0;
+            request(pl.ring + (ring_cur == 0 ? KD : ring_cur - 1) * RING_IMG, a_row, ahead);
+            // Counted by hand: stage 0 stores nothing, so behind the request of row ri exactly the 2 loads of each of the KD later
+            // requests are certain (before the first row also the 2 G loads of the resident pairs); publishes and re-reads add to them.
+            __builtin_amdgcn_s_waitcnt(wait_vmcnt(N_AFTER));
+            // The image is chosen at run time.  A plain LDS read would make the compiler wait for every load-to-LDS in flight
+            // (vmcnt(0): it cannot tell the images apart); the asm is opaque to that bookkeeping and waits for its own reads.
+            const uint32_t at = (uint32_t)(uintptr_t)GE_LDS(pl.ring + ring_cur * RING_IMG) + (uint32_t)lane * 16u;
+            ge_i4 rb, rgb;
+            asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:1024\n\ts_waitcnt lgkmcnt(0)"
+                         : "=&v"(rb), "=&v"(rgb) : "v"(at) : "memory");
+            __builtin_memcpy(&b, &rb, 16); __builtin_memcpy(&gb, &rgb, 16);
+            ring_cur = ring_cur == KD ? 0 : ring_cur + 1;
+        } else
         if constexpr (SRC == PAIR_MEM) {
             request(decltype(CUR)::value ? setA : setB, n_row, more);
             // Counted by hand (see epoch_walk's step): memory instructions complete in order, and behind this image's request at
@@ -507,8 +542,10 @@ __device__ __forceinline__ void tile_chunk(const GloveParams &p, const int32_t c
         }
         // (SRC = PAIR_LDS: the previous stage wrote the image one step ago, and the block barrier that ended that step lies between)
         asm volatile("" ::: "memory");
-        b = *reinterpret_cast<const float4 *>(img + lane * 4);
-        gb = *reinterpret_cast<const float4 *>(img + IMG_G + lane * 4);
+        if constexpr (KD == 1) {
+            b = *reinterpret_cast<const float4 *>(img + lane * 4);
+            gb = *reinterpret_cast<const float4 *>(img + IMG_G + lane * 4);
+        }
         bb = rl(b.x); gbb = rl(gb.x);
         for (int e = pos; e < nxt; ++e) {
             const int s = staged(1, e);
@@ -576,7 +613,7 @@ __device__ __forceinline__ void tile_chunk(const GloveParams &p, const int32_t c
 // PANELS (k_epoch_panels): the workgroup also walks the hub panel chunks of the layout, its four waves as the four stages of
 // tile_chunk's pipeline.  The panel chunks have a ticket counter of their own; a block below n_panel_blocks serves it first and the
 // main queue afterwards, every other block the other way round, so whichever queue runs dry first frees its blocks for the other.
-template <int VW, int NCH, int OPT, bool EMB16, bool FAT, int TG, bool PANELS = false>
+template <int VW, int NCH, int OPT, bool EMB16, bool FAT, int TG, bool PANELS = false, int KD = 1>
 __device__ __forceinline__ void epoch_walk(const GloveParams &p, const int32_t n_workers) {
     using VT = typename Vec<VW>::T;
     static_assert(!EMB16 || VW == 4, "bf16 embeddings need dim % 4 == 0");
@@ -699,11 +736,18 @@ __device__ __forceinline__ void epoch_walk(const GloveParams &p, const int32_t n
             const int32_t *const pp = p.ppos + (int64_t)pc * 9;
             const int32_t grp = rfl(pp[0]) * 4 + wib, c_lo = rfl(pp[1 + 2 * wib]), c_len = rfl(pp[2 + 2 * wib]);
             const int nx = wib < 3 ? wib + 1 : 0;          // (wave 3 has no next stage: it stores to memory)
-            const PanelLink pl{s_prow, rfl(s_pn), wib, s_setA + nx * SET_FLOATS, s_setB + nx * SET_FLOATS};
+            float *ring = nullptr;
+            if constexpr (KD > 1) {
+                // stage 0's request ring (wave 0 alone reads and fills it; the images of the ordinary walk stay the stages' hand-over)
+                static_assert(SET_FLOATS == RING_IMG && IMG_G * 2 == RING_IMG, "an image of the ring is a focus pair's");
+                __shared__ float s_ring[(KD + 1) * RING_IMG];
+                ring = s_ring;
+            }
+            const PanelLink pl{s_prow, rfl(s_pn), wib, s_setA + nx * SET_FLOATS, s_setB + nx * SET_FLOATS, ring};
             float *const tr_c = s_tr[wib][0], *const tr_g = s_tr[wib][1];
             float *const setA = s_setA + wib * SET_FLOATS, *const setB = s_setB + wib * SET_FLOATS;
             // the stage of this wave: a compile-time source and sink each (the barriers inside are counted in tile_chunk)
-            if (wib == 0) tile_chunk<TG, PAIR_MEM, PAIR_LDS>(p, c_lo, c_len, grp, setA, setB, tr_c, tr_g, s_stage[wib], cost_acc, pl, tid & 63);
+            if (wib == 0) tile_chunk<TG, PAIR_MEM, PAIR_LDS, KD>(p, c_lo, c_len, grp, setA, setB, tr_c, tr_g, s_stage[wib], cost_acc, pl, tid & 63);
             else if (wib < 3) tile_chunk<TG, PAIR_LDS, PAIR_LDS>(p, c_lo, c_len, grp, setA, setB, tr_c, tr_g, s_stage[wib], cost_acc, pl, tid & 63);
             else tile_chunk<TG, PAIR_LDS, PAIR_MEM>(p, c_lo, c_len, grp, setA, setB, tr_c, tr_g, s_stage[wib], cost_acc, pl, tid & 63);
         }
@@ -1190,6 +1234,17 @@ __global__ __launch_bounds__(256, 3) void k_epoch_tiles(GloveParams p, int32_t n
 __global__ __launch_bounds__(256, 3) void k_epoch_panels(GloveParams p, int32_t n_workers) {
     epoch_walk<4, 1, GE_OPT_ADAGRAD, false, true, TILE_G, true>(p, n_workers);
 }
+// The panel kernel with stage 0's focus pairs requested RING_K rows ahead: the same sequential program on the
+// same layout.  tests/test_hub_ring_resources.py holds its registers, its LDS and its vmcnt(2 RING_K) waits.  RING_K is the
+// sweep's choice among 2, 4, 6 (profiles/hub_ring_bench.json; -DGE_RING_K=n builds another depth); LDS bounds it at 9.
+#ifndef GE_RING_K
+#define GE_RING_K 2
+#endif
+constexpr int RING_K = GE_RING_K;
+static_assert(RING_K >= 2 && 2 * RING_K < 64, "vmcnt is a 6-bit counter");
+__global__ __launch_bounds__(256, 3) void k_epoch_ring(GloveParams p, int32_t n_workers) {
+    epoch_walk<4, 1, GE_OPT_ADAGRAD, false, true, TILE_G, true, RING_K>(p, n_workers);
+}
 
 // Placement probe: what an epoch does to a record table -- whole records read and written back at random rows, sc1 like the trainer's
 // accesses, one wavefront per stream of rows.  The values are written back unchanged (the table is not yet initialised and nobody
@@ -1543,7 +1598,7 @@ ge_status validate_config(const ge_glove_cfg *cfg, const int32_t *I, const int32
     if (emb16 && (cfg->mode != GE_MODE_HOGWILD || cfg->shuffle != GE_SHUFFLE_DEVICE || cfg->opt != GE_OPT_ADAGRAD || cfg->dim % 4 != 0))
         return ge::fail(GE_ERR_ARG, "bf16 embeddings need mode=hogwild, shuffle=device, opt=adagrad and dim %% 4 == 0 (the reference path is fp32)");
     if (cfg->hot_columns < GE_HOT_AUTO || cfg->hot_columns > GE_HOT_ALL) return ge::fail(GE_ERR_ARG, "invalid hot_columns %d", cfg->hot_columns);
-    if (cfg->hot_theta < 0 || cfg->stale_budget < 0 || cfg->flush_every < 0 || cfg->blocks_per_cu < 0 || (cfg->layout_flags & ~511) != 0)
+    if (cfg->hot_theta < 0 || cfg->stale_budget < 0 || cfg->flush_every < 0 || cfg->blocks_per_cu < 0 || (cfg->layout_flags & ~2047) != 0)
         return ge::fail(GE_ERR_ARG, "invalid tuning fields (hot_theta %g, stale_budget %g, flush_every %d, blocks_per_cu %d, layout_flags %d)",
                         (double)cfg->hot_theta, (double)cfg->stale_budget, cfg->flush_every, cfg->blocks_per_cu, cfg->layout_flags);
     int32_t rb = cfg->row_begin, re = cfg->row_end;
@@ -1706,8 +1761,10 @@ void plan_workers(ge_glove *h) { take_plan(h, plan_workers_of(h, h->hw.fn)); }
 // the bench size only; smaller handles keep their chunk table and their kernel).  GE_LAYOUT_NO_HUB_TILES: never.
 // (GE_LAYOUT_HUB_PANELS on a handle too small for tiles of its own asks for the tiles its panels are made of, as GE_LAYOUT_HUB_TILES
 // does -- unless GE_LAYOUT_NO_HUB_PANELS takes it back; from 2^25 nonzeros on the panels are made of the tiles the handle builds anyway)
+// (GE_LAYOUT_DEEP_PANELS asks for panels as GE_LAYOUT_HUB_PANELS does; GE_LAYOUT_NO_DEEP_PANELS takes back the kernel, not the panels)
+bool deep_asked(const ge_glove_cfg &cfg) { return (cfg.layout_flags & GE_LAYOUT_DEEP_PANELS) != 0; }
 bool tiles_forced(const ge_glove_cfg &cfg) {
-    const bool panels_asked = (cfg.layout_flags & (GE_LAYOUT_HUB_PANELS | GE_LAYOUT_NO_HUB_PANELS)) == GE_LAYOUT_HUB_PANELS;
+    const bool panels_asked = ((cfg.layout_flags & GE_LAYOUT_HUB_PANELS) != 0 || deep_asked(cfg)) && (cfg.layout_flags & GE_LAYOUT_NO_HUB_PANELS) == 0;
     return (cfg.layout_flags & GE_LAYOUT_HUB_TILES) != 0 || (panels_asked && cfg.nnz < ((int64_t)1 << 25));
 }
 bool tiles_possible(const ge_glove *h) {
@@ -1723,8 +1780,18 @@ bool tiles_possible(const ge_glove *h) {
 bool panels_possible(const ge_glove *h) {
     const ge_glove_cfg &cfg = h->cfg;
     if ((cfg.layout_flags & GE_LAYOUT_NO_HUB_PANELS) || !tiles_possible(h)) return false;
-    return (cfg.layout_flags & GE_LAYOUT_HUB_PANELS) != 0 || cfg.nnz >= ((int64_t)1 << 25);
+    return (cfg.layout_flags & GE_LAYOUT_HUB_PANELS) != 0 || deep_asked(cfg) || cfg.nnz >= ((int64_t)1 << 25);
 }
+// The ring kernel walks the panels of a handle that builds them by default, or under GE_LAYOUT_DEEP_PANELS; a
+// handle whose panels GE_LAYOUT_HUB_PANELS alone asked for keeps k_epoch_panels, and GE_LAYOUT_NO_DEEP_PANELS wins over everything.
+bool ring_possible(const ge_glove *h) {
+    const ge_glove_cfg &cfg = h->cfg;
+    if ((cfg.layout_flags & GE_LAYOUT_NO_DEEP_PANELS) || !panels_possible(h)) return false;
+    return deep_asked(cfg) || (cfg.layout_flags & GE_LAYOUT_HUB_PANELS) == 0;
+}
+// Hub columns of density >= 1 / PANEL_DENSITY_DIV join the panels of a handle that runs the ring kernel through the default
+// rule (glove_layout.hip; chosen by the sweep of profiles/hub_ring_bench.json).
+constexpr int PANEL_DENSITY_DIV = 16;
 
 // The order a Hogwild epoch visits the nonzeros in.  Device shuffle: the blocked layout of ge_layout.h, built on the device.
 // General order (Java permutation / matrix order): the resident side is always the context row, hub columns are keyed ~j.
@@ -1752,16 +1819,24 @@ ge_status plan_epoch_layout(ge_glove *h, const int32_t *I, const int32_t *J, con
         // and the flush limits from the workers (the hub threshold stays that of the ordinary kernel's workers: glove_layout.hip)
         const hogwild_fn tile_fn = k_epoch_tiles<TILE_G>;
         WorkerPlan tile_plan{};
+        bool ring = false;
         if (tiles_possible(h)) {
             tile_plan = plan_workers_of(h, tile_fn);
             rq.tile_g = TILE_G; rq.tile_force = tiles_forced(cfg) ? 1 : 0; rq.tile_workers = tile_plan.workers;
             if (panels_possible(h)) {
                 rq.panels = 1; rq.blocks = tile_plan.blocks;
                 if (const char *e = std::getenv("GE_PANEL_BLOCKS")) rq.panel_blocks = std::max(0, std::atoi(e));     // experiments: the sweep of profiles/hub_panels_bench.json
+                if (ring_possible(h)) {
+                    ring = true;
+                    if (!rq.tile_force) {
+                        rq.panel_div = PANEL_DENSITY_DIV;
+                        if (const char *e = std::getenv("GE_PANEL_DENSITY_DIV")) rq.panel_div = std::max(8, std::atoi(e));   // experiments: the sweep of profiles/hub_ring_bench.json
+                    }
+                }
             }
         }
         GE_CHECK(ge::build_blocked_layout(rq, I, J, X, h->stream, &h->lay));
-        if (h->lay.n_tchunks > 0 || h->lay.n_pchunks > 0) { h->hw.fn = h->lay.n_pchunks > 0 ? (hogwild_fn)k_epoch_panels : tile_fn; take_plan(h, tile_plan); }
+        if (h->lay.n_tchunks > 0 || h->lay.n_pchunks > 0) { h->hw.fn = h->lay.n_pchunks > 0 ? (ring ? (hogwild_fn)k_epoch_ring : (hogwild_fn)k_epoch_panels) : tile_fn; take_plan(h, tile_plan); }
         h->n_chunks = h->lay.n_chunks; h->n_hchunks = h->lay.n_hchunks; h->n_tchunks = h->lay.n_tchunks; h->n_pchunks = h->lay.n_pchunks;
         h->hot_cols = h->lay.hot_cols; h->hot_nnz = h->lay.hot_nnz; h->hot_threshold = h->lay.hot_threshold;
         h->flush_every = h->lay.flush_min;

@@ -141,6 +141,10 @@ struct Dev {            // frees every temporary of one build
 // 700 / 760 / 768); profiles/hub_panels_bench.json.  The panels' share of the schedule's BYTES, doubled -- the first guess -- gives
 // 82 at the bench size, where the panel loop is then the long pole and the epoch slower than without panels.
 constexpr double PANEL_STEP_COST = 0.8;
+// The ring kernel keeps the constant: with panels down to density 1/16 the bench handle gets 284 workgroups.  The
+// sweep there (206: 46.8 ms, 250: 45.0, 270: 45.3, 284: 45.6, 300: 46.0, 320: 46.4; parent 46.5; profiles/hub_ring_bench.json) has
+// its best near 250 on the slower kind of placement, but on the faster kind 261 gave no gain and 284 did, and C2's shape needs its
+// 578 for convergence: one constant for both kernels.
 
 int grid_for(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 16384)); }
 
@@ -249,17 +253,33 @@ ge_status build_blocked_layout(const LayoutRequest &rq, const int32_t *I, const 
     if (N > 0 && rq.hot_columns != GE_HOT_NONE) {
         if (G >= 2) {
             const int64_t thr_t = hub_threshold(rq.workers);
+            // Mid-density columns: where the ring kernel walks the panels, hub columns down to density 1 / panel_div
+            // are eligible -- for PANELS only: a tile group of four saves less at that density than its extra context loads cost.
+            const int64_t div = (!rq.tile_force && rq.panels && G == 4 && rq.panel_div > 8) ? (int64_t)rq.panel_div : 8;
             std::vector<int32_t> el;               // eligible columns, densest first
             for (int32_t v = 0; v < V; ++v)
-                if (cnt[(size_t)v] >= thr_t && cnt[(size_t)v] > 0 && (rq.tile_force || (int64_t)cnt[(size_t)v] * 8 >= (int64_t)rows)) el.push_back(v);
+                if (cnt[(size_t)v] >= thr_t && cnt[(size_t)v] > 0 && (rq.tile_force || (int64_t)cnt[(size_t)v] * div >= (int64_t)rows)) el.push_back(v);
             std::stable_sort(el.begin(), el.end(), [&](int32_t a, int32_t b) { return cnt[(size_t)a] > cnt[(size_t)b]; });
-            size_t n_el = el.size();
-            if (n_el % (size_t)G == 1) --n_el;     // a last group of one column stays with the ordinary hub chunks
-            const uint64_t groups = (n_el + (size_t)G - 1) / (size_t)G;
+            size_t n_dense = el.size();            // the columns of density >= 1/8 (all of them unless panel_div admits more): a prefix
+            if (div > 8) { n_dense = 0; while (n_dense < el.size() && (int64_t)cnt[(size_t)el[n_dense]] * 8 >= (int64_t)rows) ++n_dense; }
             // The sort key is 32 bits wide, and the build counts the nonzeros of every (group, row) in a dense table (4 bytes each, on
             // the device and on the host): bounded under the default gate (columns of density >= 1/8: at most 8 N / rows columns,
             // so at most 2 N pairs), not under GE_LAYOUT_HUB_TILES.  Too large: no tiles by default, an error where they were asked for.
-            if (groups * (uint64_t)rows * (uint64_t)G + (uint64_t)V + (uint64_t)rows >= ((uint64_t)1 << 32) || groups * (uint64_t)rows > ((uint64_t)1 << 28)) {
+            auto too_large = [&](uint64_t groups) {
+                return groups * (uint64_t)rows * (uint64_t)G + (uint64_t)V + (uint64_t)rows >= ((uint64_t)1 << 32) || groups * (uint64_t)rows > ((uint64_t)1 << 28);
+            };
+            // Of `adm` admitted columns the full sixteens are panels; of the rest only the dense ones stay, as tile groups, and the
+            // others go back to the column-major hub chunks.  Past the table's bound the sparsest sixteen are dropped until it
+            // holds; with no mid-density column left this is the rule of a handle without them.
+            size_t adm = el.size(), n_el = 0;
+            for (;;) {
+                n_el = std::max(adm / 16 * 16, n_dense);
+                if (n_el % (size_t)G == 1) --n_el; // a last group of one column stays with the ordinary hub chunks
+                if (adm <= n_dense || !too_large((n_el + (size_t)G - 1) / (size_t)G)) break;
+                adm = std::max(n_dense, adm / 16 * 16 - (adm % 16 == 0 ? 16 : 0));
+            }
+            const uint64_t groups = (n_el + (size_t)G - 1) / (size_t)G;
+            if (too_large(groups)) {
                 if (rq.tile_force && n_el >= 2)
                     return ge::fail(GE_ERR_ARG, "layout hub_tiles: %llu column groups x %d rows are too many for the tile build (forced tiles are for small matrices)",
                                     (unsigned long long)groups, rows);
@@ -412,6 +432,7 @@ ge_status build_blocked_layout(const LayoutRequest &rq, const int32_t *I, const 
         if (clk.on) std::fprintf(stderr, "[ge_glove_create]   layout: panel steps %lld, chunks %lld, main nonzeros %lld\n", (long long)panel_steps, (long long)out->n_pchunks, (long long)(N - nP));
         if (pb <= 0) pb = (int32_t)std::lround(w_panels / std::max(w_panels + w_main, 1.0) * (double)rq.blocks);
         out->panel_blocks = std::max(1, std::min(pb, std::max(rq.blocks, 1)));
+        if (clk.on) std::fprintf(stderr, "[ge_glove_create]   layout: %d panels, %d of %d workgroups start in the panel loop\n", n_panels, out->panel_blocks, rq.blocks);
         // The staleness rule with the K of a panel: every block inside the panel holds all its columns, and of the blocks in the
         // panel loop the panel's share of the panel chunks are inside it.
         for (int32_t pn = 0; pn < n_panels; ++pn) {

@@ -436,6 +436,8 @@ struct Configuration {
                             else if (nm == "no_hub_tiles") c.device.layout_flags |= GE_LAYOUT_NO_HUB_TILES;
                             else if (nm == "hub_panels") c.device.layout_flags |= GE_LAYOUT_HUB_PANELS;
                             else if (nm == "no_hub_panels") c.device.layout_flags |= GE_LAYOUT_NO_HUB_PANELS;
+                            else if (nm == "deep_panels") c.device.layout_flags |= GE_LAYOUT_DEEP_PANELS;
+                            else if (nm == "no_deep_panels") c.device.layout_flags |= GE_LAYOUT_NO_DEEP_PANELS;
                             else if (!nm.empty() && nm != "default") throw std::invalid_argument("device.layout: unknown flag " + nm);
                         }
                     }

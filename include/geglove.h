@@ -238,10 +238,18 @@ typedef struct {
  *                once per 16 columns; groups that fill no panel stay tiles.  Default: handles that build hub tiles by default (>= 2^25
  *                nonzeros).  Under this flag a smaller handle builds its panels from forced tiles, as under HUB_TILES (tests, small
  *                matrices).
- * NO_HUB_PANELS  never build hub panels (wins over HUB_PANELS): the handle's layout, kernel and results are those of a library
- *                without panels. */
+ * NO_HUB_PANELS  never build hub panels (wins over HUB_PANELS and DEEP_PANELS): the handle's layout, kernel and results are those of a
+ *                library without panels.
+ * DEEP_PANELS    hub panels walked by the ring kernel: stage 0 of the panel pipeline keeps the focus pairs of
+ *                several rows in flight instead of one.  Forces panels at any size as HUB_PANELS does (a handle below 2^25 nonzeros
+ *                builds them from forced tiles, every hub column eligible); the same layout, the same sequential program.  Default:
+ *                handles that build hub panels by default, unless HUB_PANELS is set -- a HUB_PANELS handle without this flag keeps
+ *                the one-row-ahead kernel.
+ * NO_DEEP_PANELS never run the ring kernel (wins over DEEP_PANELS and over the default): the handle's layout, kernel and results are
+ *                those of a library without it. */
 enum { GE_LAYOUT_FIXED_CUTS = 1, GE_LAYOUT_PLAIN_LONG_ROWS = 2, GE_LAYOUT_SEPARATE_TABLES = 4, GE_LAYOUT_PACKED_RECORDS = 8, GE_LAYOUT_FIRST_PLACEMENT = 16,
-       GE_LAYOUT_HUB_TILES = 32, GE_LAYOUT_NO_HUB_TILES = 64, GE_LAYOUT_HUB_PANELS = 128, GE_LAYOUT_NO_HUB_PANELS = 256 };
+       GE_LAYOUT_HUB_TILES = 32, GE_LAYOUT_NO_HUB_TILES = 64, GE_LAYOUT_HUB_PANELS = 128, GE_LAYOUT_NO_HUB_PANELS = 256,
+       GE_LAYOUT_DEEP_PANELS = 512, GE_LAYOUT_NO_DEEP_PANELS = 1024 };
 
 /* What the library decided for a handle (reporting / DESIGN.md numbers). */
 typedef struct {

@@ -613,7 +613,10 @@ __device__ __forceinline__ void tile_chunk(const GloveParams &p, const int32_t c
 // PANELS (k_epoch_panels): the workgroup also walks the hub panel chunks of the layout, its four waves as the four stages of
 // tile_chunk's pipeline.  The panel chunks have a ticket counter of their own; a block below n_panel_blocks serves it first and the
 // main queue afterwards, every other block the other way round, so whichever queue runs dry first frees its blocks for the other.
-template <int VW, int NCH, int OPT, bool EMB16, bool FAT, int TG, bool PANELS = false, int KD = 1>
+// WD: how many nonzeros ahead the ordinary walk requests its streamed pair.  1: the next nonzero's, into the other
+// of two images (every kernel but k_epoch_walk2).  2: the pair of nonzero pos + 2 is requested at the top of step pos into the
+// third of three images, and the image of nonzero pos is read behind vmcnt(2 N_TAB + 2 N_DMA).
+template <int VW, int NCH, int OPT, bool EMB16, bool FAT, int TG, bool PANELS = false, int KD = 1, int WD = 1>
 __device__ __forceinline__ void epoch_walk(const GloveParams &p, const int32_t n_workers) {
     using VT = typename Vec<VW>::T;
     static_assert(!EMB16 || VW == 4, "bf16 embeddings need dim % 4 == 0");
@@ -763,6 +766,13 @@ __device__ __forceinline__ void epoch_walk(const GloveParams &p, const int32_t n
     }
     const int lane = tid & 63;
     float *const setA = s_setA + (tid >> 6) * SET_FLOATS, *const setB = s_setB + (tid >> 6) * SET_FLOATS;
+    float *setC = nullptr;
+    if constexpr (WD > 1) {
+        // the third image of the depth-2 walk: an array of its own, like the other two (the wait for one never covers another)
+        static_assert(WD == 2, "the walk is one or two nonzeros deep");
+        __shared__ float s_setC[4 * SET_FLOATS];
+        setC = s_setC + (tid >> 6) * SET_FLOATS;
+    }
     bool inr[NCH];                          // lane holds real elements of a row (D % VW == 0)
 #pragma unroll
     for (int q = 0; q < NCH; ++q) inr[q] = (lane + q * 64) * VW < D;
@@ -973,7 +983,17 @@ __device__ __forceinline__ void epoch_walk(const GloveParams &p, const int32_t n
             const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(lb >> 32), sln);
             n_l = __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
         };
-        // Requests the streamed rows of nonzero n_oth into set SET (0: A, 1: B).  `live` false: the same instructions against
+        // WD 2: the fields of the nonzero behind the next one, decoded with the next one's left as they are.  (A wrapper, and named
+        // in discarded branches only where WD is 1: decode() itself and what the walk's lambdas capture stay what they were, and
+        // with them every older kernel's code, DESIGN.md 3.1.4.  The same goes for request_ahead and the third image below.)
+        int32_t m_oth = 0, m_key = KEY_PAD; float m_w = 0.0f; double m_l = 0.0;
+        auto decode_ahead = [&](int pos) {
+            const int32_t k = n_key, o = n_oth; const float w = n_w; const double l = n_l;
+            decode(pos);
+            m_key = n_key; m_oth = n_oth; m_w = n_w; m_l = n_l;
+            n_key = k; n_oth = o; n_w = w; n_l = l;
+        };
+        // Requests the streamed rows of nonzero n_oth into set SET (0: A, 1: B, 2: C).  `live` false: the same instructions against
         // zero-sized resources -- nothing is read, zeros arrive.  Issued on EVERY step, so that the number of memory
         // instructions between a request and its use is the same on every path and the wait can be counted.
         auto request_streamed = [&](auto SET, const bool live) {
@@ -983,7 +1003,8 @@ __device__ __forceinline__ void epoch_walk(const GloveParams &p, const int32_t n
             else rb = make_rsrc(B_rows + (int64_t)n_oth * DS, rbytes);
             const __amdgpu_buffer_rsrc_t rg = make_rsrc(B_gs + (int64_t)n_oth * DS, rbytes);
             const __amdgpu_buffer_rsrc_t rh = make_rsrc(B_m2 + (int64_t)n_oth * DS, MOM ? rbytes : 0u);
-            float *const img = decltype(SET)::value ? setB : setA;
+            float *img = decltype(SET)::value ? setB : setA;
+            if constexpr (WD > 1) { if constexpr (decltype(SET)::value == 2) img = setC; }
 #pragma unroll
             for (int j = 0; j < (IMG_R / IMG) * N_Q; ++j)
                 load_to_lds<(VW == 4 ? 16 : 4)>(rb, img + j * (IMG / N_Q), (lane + j * 64) * DMAW);
@@ -998,6 +1019,11 @@ __device__ __forceinline__ void epoch_walk(const GloveParams &p, const int32_t n
                 if constexpr (MOM) load_to_lds<4>(make_rsrc(B_m2b + n_oth, four), img + IMG_B + 128, lane * 4);
             }
             asm volatile("" ::: "memory");          // issued here, not where the scheduler would like them
+        };
+        // WD 2: the same for the nonzero behind the next one
+        auto request_ahead = [&](auto SET, const bool live) {
+            const int32_t o = n_oth;
+            n_oth = m_oth; request_streamed(SET, live); n_oth = o;
         };
         // waits until everything requested so far has arrived
         auto settle = [&]() { __builtin_amdgcn_s_waitcnt(wait_vmcnt(0)); asm volatile("" ::: "memory"); };
@@ -1036,15 +1062,18 @@ __device__ __forceinline__ void epoch_walk(const GloveParams &p, const int32_t n
         // the staged nonzeros have arrived before the walk starts: inside it only row traffic is pending
         asm volatile("" : "+v"(oth[0]), "+v"(oth[1]), "+v"(ww[0]), "+v"(ww[1]), "+v"(ll[0]), "+v"(ll[1]));
         bool again = false, recut = false;
+        bool again2 = false;                  // WD 2: `again` of the step behind this one
         // One nonzero.  CUR (0 / 1) names the set that holds its streamed rows; the other set is requested for the next one first
-        // thing, before this step waits for anything.
+        // thing, before this step waits for anything.  (WD 2: CUR is 0 / 1 / 2, and the set requested is the one that held the
+        // previous nonzero's rows, for the nonzero behind the next one.)
         auto step = [&](const int pos, auto CUR) {
-            constexpr std::integral_constant<int, 1 - decltype(CUR)::value> NXT{};
+            constexpr std::integral_constant<int, WD == 1 ? 1 - decltype(CUR)::value : (decltype(CUR)::value + 2) % 3> NXT{};
             const int32_t b_id = n_oth, skey = n_key;
             const float w = n_w; const double l = n_l;
             // the previous nonzero had the same streamed row: what was requested before its stores is stale.  Re-read behind
             // them (same wave, same address: in order) and wait right here, so that on the common path the set is known to be
             // older than those stores and the wait for it leaves them in flight.
+            // (WD 2: the set was requested in front of the stores of the two previous nonzeros, and is stale if either had this row.)
             if (again) { request_streamed(CUR, true); settle(); again = false; }
             // the previous step cut its run and this one continues on the same resident row: requested here, behind that publish
             if (recut) { request_resident(); recut = false; }
@@ -1058,13 +1087,30 @@ __device__ __forceinline__ void epoch_walk(const GloveParams &p, const int32_t n
             }
             const bool last = pos + 1 >= n_valid;
             bool next_new = false;
-            if (!last) {
-                decode(pos + 1);
-                again = n_oth == b_id;
-                // a long hub run is cut every flush_lim nonzeros: publish the delta, re-read what the other workers published
-                next_new = n_key != skey || (cur_hot && run_len + 1 >= flush_lim);
+            if constexpr (WD == 1) {
+                if (!last) {
+                    decode(pos + 1);
+                    again = n_oth == b_id;
+                    // a long hub run is cut every flush_lim nonzeros: publish the delta, re-read what the other workers published
+                    next_new = n_key != skey || (cur_hot && run_len + 1 >= flush_lim);
+                }
+                request_streamed(NXT, !last);
+            } else {
+                // the next nonzero was decoded a step ago, and whether its set is stale was decided then
+                if (!last) {
+                    n_key = m_key; n_oth = m_oth; n_w = m_w; n_l = m_l;
+                    again = again2;
+                    next_new = n_key != skey || (cur_hot && run_len + 1 >= flush_lim);
+                }
+                // the one behind it: its set is requested in front of this nonzero's stores and the next one's
+                const bool ahead = pos + 2 < n_valid;           // (no request crosses the end of the chunk)
+                again2 = false;
+                if (ahead) {
+                    decode_ahead(pos + 2);
+                    again2 = m_oth == n_oth || m_oth == b_id;
+                }
+                request_ahead(NXT, ahead);
             }
-            request_streamed(NXT, !last);
             if (open_new) {
 #pragma unroll
                 for (int q = 0; q < NCH; ++q) {
@@ -1097,11 +1143,14 @@ __device__ __forceinline__ void epoch_walk(const GloveParams &p, const int32_t n
             // table and chunk as well; then the request for the other set a few lines up.
             constexpr int N_TAB = NCH * (2 + (MOM ? 1 : 0)) + (FAT ? 0 : 2 + (MOM ? 1 : 0));
             constexpr int N_DMA = ((IMG_R / IMG) + NCH * (1 + (MOM ? 1 : 0))) * N_Q + (FAT ? 0 : 2 + (MOM ? 1 : 0));
-            constexpr int N_AFTER = N_TAB + N_DMA;
+            // (WD 2: behind this set's request stand the stores of the two previous steps and the requests of the previous step and of
+            // this one; before the first steps the chunk's prologue issues as many, see below.)
+            constexpr int N_AFTER = WD * (N_TAB + N_DMA);
             static_assert(N_AFTER < 64, "vmcnt is a 6-bit counter");
             __builtin_amdgcn_s_waitcnt(wait_vmcnt(N_AFTER));       // the builtin, not asm text: the compiler's bookkeeping sees it
             asm volatile("" ::: "memory");
-            const float *const img = decltype(CUR)::value ? setB : setA;
+            const float *img = decltype(CUR)::value ? setB : setA;
+            if constexpr (WD > 1) { if constexpr (decltype(CUR)::value == 2) img = setC; }
 #pragma unroll
             for (int q = 0; q < NCH; ++q) {
                 if constexpr (EMB16) bl[q] = widen_bf16x4(*reinterpret_cast<const float2 *>(img + (lane + q * 64) * 2));
@@ -1205,10 +1254,39 @@ __device__ __forceinline__ void epoch_walk(const GloveParams &p, const int32_t n
         };
         constexpr std::integral_constant<int, 0> SET_A{};
         constexpr std::integral_constant<int, 1> SET_B{};
-        if (n_valid > 0) { decode(0); request_streamed(SET_A, true); request_resident(); }
-        for (int pos = 0; pos < n_valid; pos += 2) {
-            step(pos, SET_A);
-            if (pos + 1 < n_valid) step(pos + 1, SET_B);
+        if constexpr (WD == 1) {
+            if (n_valid > 0) { decode(0); request_streamed(SET_A, true); request_resident(); }
+            for (int pos = 0; pos < n_valid; pos += 2) {
+                step(pos, SET_A);
+                if (pos + 1 < n_valid) step(pos + 1, SET_B);
+            }
+        } else {
+            constexpr std::integral_constant<int, 2> SET_C{};
+            if (n_valid > 0) {
+                // Step 0 reads set A behind the same count as every later step: behind its request stand a step's stores against a
+                // zero-sized resource (nothing is written), the request of nonzero 1, the resident rows' loads in the place of a
+                // step's stores, and step 0's own request.  Step 1 finds those loads, step 0's request and stores and its own
+                // request behind the request of nonzero 1.
+                decode(0);
+                request_streamed(SET_A, true);
+                constexpr int N_TAB = NCH * (2 + (MOM ? 1 : 0)) + (FAT ? 0 : 2 + (MOM ? 1 : 0));       // as in step
+#pragma unroll
+                for (int j = 0; j < N_TAB; ++j) __builtin_amdgcn_raw_buffer_store_b32(lane, make_rsrc(B_rows, 0u), lane * 4, 0, AUX_SC1);
+                asm volatile("" ::: "memory");
+                const bool two = n_valid > 1;
+                if (two) { decode_ahead(1); again2 = m_oth == n_oth; }
+                request_ahead(SET_B, two);
+                request_resident();
+            }
+            // (one way out per step, so that no path leads from the first step to the third past the second: the compiler counts
+            // the instructions behind set C's request along every path it sees, and would wait for fewer than there are)
+            for (int pos = 0; pos < n_valid; pos += 3) {
+                step(pos, SET_A);
+                if (pos + 1 >= n_valid) break;
+                step(pos + 1, SET_B);
+                if (pos + 2 >= n_valid) break;
+                step(pos + 2, SET_C);
+            }
         }
     }
     }
@@ -1244,6 +1322,12 @@ constexpr int RING_K = GE_RING_K;
 static_assert(RING_K >= 2 && 2 * RING_K < 64, "vmcnt is a 6-bit counter");
 __global__ __launch_bounds__(256, 3) void k_epoch_ring(GloveParams p, int32_t n_workers) {
     epoch_walk<4, 1, GE_OPT_ADAGRAD, false, true, TILE_G, true, RING_K>(p, n_workers);
+}
+// The ring kernel with the ordinary walk two nonzeros deep: a worker keeps two streamed pairs in flight, in three
+// images per wave.  The same sequential program on the same layout; tests/test_deep_walk_resources.py holds its registers, its LDS
+// (the ring kernel's and a third image per wave) and its vmcnt(8) waits.
+__global__ __launch_bounds__(256, 3) void k_epoch_walk2(GloveParams p, int32_t n_workers) {
+    epoch_walk<4, 1, GE_OPT_ADAGRAD, false, true, TILE_G, true, RING_K, 2>(p, n_workers);
 }
 
 // Placement probe: what an epoch does to a record table -- whole records read and written back at random rows, sc1 like the trainer's
@@ -1598,7 +1682,7 @@ ge_status validate_config(const ge_glove_cfg *cfg, const int32_t *I, const int32
     if (emb16 && (cfg->mode != GE_MODE_HOGWILD || cfg->shuffle != GE_SHUFFLE_DEVICE || cfg->opt != GE_OPT_ADAGRAD || cfg->dim % 4 != 0))
         return ge::fail(GE_ERR_ARG, "bf16 embeddings need mode=hogwild, shuffle=device, opt=adagrad and dim %% 4 == 0 (the reference path is fp32)");
     if (cfg->hot_columns < GE_HOT_AUTO || cfg->hot_columns > GE_HOT_ALL) return ge::fail(GE_ERR_ARG, "invalid hot_columns %d", cfg->hot_columns);
-    if (cfg->hot_theta < 0 || cfg->stale_budget < 0 || cfg->flush_every < 0 || cfg->blocks_per_cu < 0 || (cfg->layout_flags & ~2047) != 0)
+    if (cfg->hot_theta < 0 || cfg->stale_budget < 0 || cfg->flush_every < 0 || cfg->blocks_per_cu < 0 || (cfg->layout_flags & ~8191) != 0)
         return ge::fail(GE_ERR_ARG, "invalid tuning fields (hot_theta %g, stale_budget %g, flush_every %d, blocks_per_cu %d, layout_flags %d)",
                         (double)cfg->hot_theta, (double)cfg->stale_budget, cfg->flush_every, cfg->blocks_per_cu, cfg->layout_flags);
     int32_t rb = cfg->row_begin, re = cfg->row_end;
@@ -1762,7 +1846,8 @@ void plan_workers(ge_glove *h) { take_plan(h, plan_workers_of(h, h->hw.fn)); }
 // (GE_LAYOUT_HUB_PANELS on a handle too small for tiles of its own asks for the tiles its panels are made of, as GE_LAYOUT_HUB_TILES
 // does -- unless GE_LAYOUT_NO_HUB_PANELS takes it back; from 2^25 nonzeros on the panels are made of the tiles the handle builds anyway)
 // (GE_LAYOUT_DEEP_PANELS asks for panels as GE_LAYOUT_HUB_PANELS does; GE_LAYOUT_NO_DEEP_PANELS takes back the kernel, not the panels)
-bool deep_asked(const ge_glove_cfg &cfg) { return (cfg.layout_flags & GE_LAYOUT_DEEP_PANELS) != 0; }
+// (GE_LAYOUT_DEEP_WALK asks for everything GE_LAYOUT_DEEP_PANELS asks for, and for the depth-2 walk on top)
+bool deep_asked(const ge_glove_cfg &cfg) { return (cfg.layout_flags & (GE_LAYOUT_DEEP_PANELS | GE_LAYOUT_DEEP_WALK)) != 0; }
 bool tiles_forced(const ge_glove_cfg &cfg) {
     const bool panels_asked = ((cfg.layout_flags & GE_LAYOUT_HUB_PANELS) != 0 || deep_asked(cfg)) && (cfg.layout_flags & GE_LAYOUT_NO_HUB_PANELS) == 0;
     return (cfg.layout_flags & GE_LAYOUT_HUB_TILES) != 0 || (panels_asked && cfg.nnz < ((int64_t)1 << 25));
@@ -1788,6 +1873,13 @@ bool ring_possible(const ge_glove *h) {
     const ge_glove_cfg &cfg = h->cfg;
     if ((cfg.layout_flags & GE_LAYOUT_NO_DEEP_PANELS) || !panels_possible(h)) return false;
     return deep_asked(cfg) || (cfg.layout_flags & GE_LAYOUT_HUB_PANELS) == 0;
+}
+// The depth-2 walk is the ring kernel's, under GE_LAYOUT_DEEP_WALK only: measured at the bench size it gains 0.8 %
+// on one kind of placement, nothing on the other, and ends at a higher cost on both, so no handle runs it by default.  GE_LAYOUT_NO_DEEP_WALK wins.
+bool walk2_possible(const ge_glove *h) {
+    const ge_glove_cfg &cfg = h->cfg;
+    if ((cfg.layout_flags & GE_LAYOUT_NO_DEEP_WALK) || !ring_possible(h)) return false;
+    return (cfg.layout_flags & GE_LAYOUT_DEEP_WALK) != 0;
 }
 // Hub columns of density >= 1 / PANEL_DENSITY_DIV join the panels of a handle that runs the ring kernel through the default
 // rule (glove_layout.hip; chosen by the sweep of profiles/hub_ring_bench.json).
@@ -1836,7 +1928,7 @@ ge_status plan_epoch_layout(ge_glove *h, const int32_t *I, const int32_t *J, con
             }
         }
         GE_CHECK(ge::build_blocked_layout(rq, I, J, X, h->stream, &h->lay));
-        if (h->lay.n_tchunks > 0 || h->lay.n_pchunks > 0) { h->hw.fn = h->lay.n_pchunks > 0 ? (ring ? (hogwild_fn)k_epoch_ring : (hogwild_fn)k_epoch_panels) : tile_fn; take_plan(h, tile_plan); }
+        if (h->lay.n_tchunks > 0 || h->lay.n_pchunks > 0) { h->hw.fn = h->lay.n_pchunks > 0 ? (ring ? (walk2_possible(h) ? (hogwild_fn)k_epoch_walk2 : (hogwild_fn)k_epoch_ring) : (hogwild_fn)k_epoch_panels) : tile_fn; take_plan(h, tile_plan); }
         h->n_chunks = h->lay.n_chunks; h->n_hchunks = h->lay.n_hchunks; h->n_tchunks = h->lay.n_tchunks; h->n_pchunks = h->lay.n_pchunks;
         h->hot_cols = h->lay.hot_cols; h->hot_nnz = h->lay.hot_nnz; h->hot_threshold = h->lay.hot_threshold;
         h->flush_every = h->lay.flush_min;

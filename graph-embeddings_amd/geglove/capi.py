@@ -23,6 +23,7 @@ GE_LAYOUT_FIXED_CUTS, GE_LAYOUT_PLAIN_LONG_ROWS, GE_LAYOUT_SEPARATE_TABLES, GE_L
 GE_LAYOUT_HUB_TILES, GE_LAYOUT_NO_HUB_TILES = 32, 64
 GE_LAYOUT_HUB_PANELS, GE_LAYOUT_NO_HUB_PANELS = 128, 256
 GE_LAYOUT_DEEP_PANELS, GE_LAYOUT_NO_DEEP_PANELS = 512, 1024
+GE_LAYOUT_DEEP_WALK, GE_LAYOUT_NO_DEEP_WALK = 2048, 4096
 (GE_STATE_FOCUS, GE_STATE_CONTEXT, GE_STATE_FBIAS, GE_STATE_CBIAS, GE_STATE_GSQ_FOCUS,
  GE_STATE_GSQ_CONTEXT, GE_STATE_GSQ_FBIAS, GE_STATE_GSQ_CBIAS, GE_STATE_M2_FOCUS, GE_STATE_M2_CONTEXT,
  GE_STATE_M2_FBIAS, GE_STATE_M2_CBIAS) = range(12)

@@ -43,7 +43,7 @@ class Configuration:
       mode: hogwild|deterministic|stratified   strata: <P, 0 = default>   shuffle: java|device|none   seed: <long>   id: <ordinal>
       hot: auto|none|all   workers: <int>   dtype: f32|bf16
       hot_theta, stale_budget, flush_every, blocks_per_cu (ge_glove_cfg; 0 / absent = library default)
-      layout: [fixed_cuts, plain_long_rows, separate_tables, packed_records, first_placement, hub_tiles, no_hub_tiles, hub_panels, no_hub_panels, deep_panels, no_deep_panels]   bca_table_slots, bca_pool_entries (ge_bca_cfg sizing)
+      layout: [fixed_cuts, plain_long_rows, separate_tables, packed_records, first_placement, hub_tiles, no_hub_tiles, hub_panels, no_hub_panels, deep_panels, no_deep_panels, deep_walk, no_deep_walk]   bca_table_slots, bca_pool_entries (ge_bca_cfg sizing)
     """
 
     def __init__(self, d=None):
@@ -260,7 +260,8 @@ _LAYOUT = {"default": 0, "fixed_cuts": capi.GE_LAYOUT_FIXED_CUTS, "plain_long_ro
            "separate_tables": capi.GE_LAYOUT_SEPARATE_TABLES, "packed_records": capi.GE_LAYOUT_PACKED_RECORDS,
            "first_placement": capi.GE_LAYOUT_FIRST_PLACEMENT, "hub_tiles": capi.GE_LAYOUT_HUB_TILES, "no_hub_tiles": capi.GE_LAYOUT_NO_HUB_TILES,
            "hub_panels": capi.GE_LAYOUT_HUB_PANELS, "no_hub_panels": capi.GE_LAYOUT_NO_HUB_PANELS,
-           "deep_panels": capi.GE_LAYOUT_DEEP_PANELS, "no_deep_panels": capi.GE_LAYOUT_NO_DEEP_PANELS}
+           "deep_panels": capi.GE_LAYOUT_DEEP_PANELS, "no_deep_panels": capi.GE_LAYOUT_NO_DEEP_PANELS,
+           "deep_walk": capi.GE_LAYOUT_DEEP_WALK, "no_deep_walk": capi.GE_LAYOUT_NO_DEEP_WALK}
 
 
 class Adagrad:

@@ -438,6 +438,8 @@ struct Configuration {
                             else if (nm == "no_hub_panels") c.device.layout_flags |= GE_LAYOUT_NO_HUB_PANELS;
                             else if (nm == "deep_panels") c.device.layout_flags |= GE_LAYOUT_DEEP_PANELS;
                             else if (nm == "no_deep_panels") c.device.layout_flags |= GE_LAYOUT_NO_DEEP_PANELS;
+                            else if (nm == "deep_walk") c.device.layout_flags |= GE_LAYOUT_DEEP_WALK;
+                            else if (nm == "no_deep_walk") c.device.layout_flags |= GE_LAYOUT_NO_DEEP_WALK;
                             else if (!nm.empty() && nm != "default") throw std::invalid_argument("device.layout: unknown flag " + nm);
                         }
                     }

@@ -246,10 +246,16 @@ typedef struct {
  *                handles that build hub panels by default, unless HUB_PANELS is set -- a HUB_PANELS handle without this flag keeps
  *                the one-row-ahead kernel.
  * NO_DEEP_PANELS never run the ring kernel (wins over DEEP_PANELS and over the default): the handle's layout, kernel and results are
- *                those of a library without it. */
+ *                those of a library without it.
+ * DEEP_WALK      the ring kernel with the ordinary walk two nonzeros deep: a worker keeps the streamed pairs of
+ *                the next two nonzeros in flight instead of one.  Forces what DEEP_PANELS forces; the same layout, the same
+ *                sequential program.  Never the default: at the bench size it is no faster than the ring kernel and the racing
+ *                workers end at a higher cost -- experiments and tests.
+ * NO_DEEP_WALK   never run the depth-2 walk (wins over DEEP_WALK): the handle's layout, kernel and results are those of a library
+ *                without it. */
 enum { GE_LAYOUT_FIXED_CUTS = 1, GE_LAYOUT_PLAIN_LONG_ROWS = 2, GE_LAYOUT_SEPARATE_TABLES = 4, GE_LAYOUT_PACKED_RECORDS = 8, GE_LAYOUT_FIRST_PLACEMENT = 16,
        GE_LAYOUT_HUB_TILES = 32, GE_LAYOUT_NO_HUB_TILES = 64, GE_LAYOUT_HUB_PANELS = 128, GE_LAYOUT_NO_HUB_PANELS = 256,
-       GE_LAYOUT_DEEP_PANELS = 512, GE_LAYOUT_NO_DEEP_PANELS = 1024 };
+       GE_LAYOUT_DEEP_PANELS = 512, GE_LAYOUT_NO_DEEP_PANELS = 1024, GE_LAYOUT_DEEP_WALK = 2048, GE_LAYOUT_NO_DEEP_WALK = 4096 };
 
 /* What the library decided for a handle (reporting / DESIGN.md numbers). */
 typedef struct {

@@ -248,7 +248,7 @@ struct ge_rank {
     ge_glove *glove = nullptr;
     ge::EvalView view{};
     int64_t n = 0, nf = 0;               // pairs; filter entries in all
-    int32_t d4 = 0;
+    int32_t d4 = 0, ranges = 0;          // ranges: the candidate ranges of the last run's grid
     int32_t *dI = nullptr, *dJ = nullptr, *dfk = nullptr, *dfidx = nullptr, *dcnt = nullptr;
     float *dq = nullptr, *dx = nullptr, *dcb = nullptr, *dzt = nullptr;
     std::vector<int32_t> cnt;            // the counts on the host: rank = 1 + cnt
@@ -387,6 +387,7 @@ ge_status rank_run_impl(ge_rank *r, int32_t *out_rank, float *out_score, ge_rank
     const int64_t want = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(ctiles, 1024), (2048 + qtiles - 1) / qtiles));
     const int64_t range_tiles = (ctiles + want - 1) / want;
     const int64_t ranges = (ctiles + range_tiles - 1) / range_tiles, range_len = range_tiles * RC_TC;
+    r->ranges = (int32_t)ranges;
     hipLaunchKernelGGL(k_rank_count, dim3((unsigned)qtiles, (unsigned)ranges), dim3(256), 0, stream, (const float *)r->dq, n, (const float *)r->dx,
                        (const float *)r->dcb, V, D4, range_len, (const float *)r->dzt, (const int32_t *)r->dJ, r->dcnt);
     GE_HIP(hipGetLastError());
@@ -439,6 +440,15 @@ ge_status ge_rank_last_phase_ms(const ge_rank *r, float *stage_ms, float *gather
     if (stage_ms) *stage_ms = r->stage_ms;
     if (gather_ms) *gather_ms = r->gather_ms;
     if (count_ms) *count_ms = r->count_ms;
+    return GE_OK;
+}
+
+ge_status ge_rank_get(const ge_rank *r, int64_t *n, int64_t *candidates, int32_t *dim, int32_t *ranges) {
+    if (!r) return ge::fail(GE_ERR_ARG, "null ge_rank handle");
+    if (n) *n = r->n;
+    if (candidates) *candidates = r->view.vocab_size;
+    if (dim) *dim = r->view.dim;
+    if (ranges) *ranges = r->ranges;
     return GE_OK;
 }
 

@@ -47,7 +47,7 @@ SYMBOLS = (
     "ge_synth_cfg_default", "ge_synth_cfg_size", "ge_synth_coo", "ge_coo_device", "ge_coo_synth_stats", "ge_glove_create_coo",
     "ge_glove_eval_create", "ge_glove_eval_run", "ge_eval_last_kernel_ms", "ge_eval_get", "ge_eval_destroy", "ge_holdout_mask",
     "ge_glove_set_arith", "ge_glove_get_arith",
-    "ge_glove_rank_create", "ge_glove_rank_run", "ge_rank_last_kernel_ms", "ge_rank_last_phase_ms", "ge_rank_summary_size", "ge_rank_destroy",
+    "ge_glove_rank_create", "ge_glove_rank_run", "ge_rank_last_kernel_ms", "ge_rank_last_phase_ms", "ge_rank_get", "ge_rank_summary_size", "ge_rank_destroy",
     "ge_kmeans_cfg_default", "ge_kmeans_cfg_size", "ge_kmeans_create", "ge_glove_kmeans_create", "ge_kmeans_set_centroids", "ge_kmeans_step",
     "ge_kmeans_run", "ge_kmeans_get", "ge_kmeans_last_kernel_ms", "ge_kmeans_destroy",
     "ge_glove_predict_create", "ge_glove_predict_run", "ge_predict_last_kernel_ms", "ge_predict_get", "ge_predict_destroy",
@@ -643,6 +643,7 @@ def _declare_rank(L):
     L.ge_glove_rank_run.argtypes = [vp, i32p, f32p, C.POINTER(RankSummary)]
     L.ge_rank_last_kernel_ms.argtypes = [vp, f32p]
     L.ge_rank_last_phase_ms.argtypes = [vp, f32p, f32p, f32p]
+    L.ge_rank_get.argtypes = [vp, i64p, i64p, i32p, i32p]
     L.ge_rank_destroy.argtypes = [vp]; L.ge_rank_destroy.restype = None
 
 
@@ -689,6 +690,12 @@ class Ranking:
         a, b, c = C.c_float(), C.c_float(), C.c_float()
         check(lib().ge_rank_last_phase_ms(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
+
+    def get(self):
+        """{n, candidates, dim, ranges}: ranges = the candidate ranges of the last run's grid (0 before the first run)."""
+        n, m, d, r = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int32()
+        check(lib().ge_rank_get(self._h, C.byref(n), C.byref(m), C.byref(d), C.byref(r)))
+        return {"n": n.value, "candidates": m.value, "dim": d.value, "ranges": r.value}
 
     def close(self):
         if self._h:

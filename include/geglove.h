@@ -825,6 +825,9 @@ ge_status ge_glove_rank_run(ge_rank *r, int32_t *out_rank, float *out_score, ge_
 ge_status ge_rank_last_kernel_ms(const ge_rank *r, float *ms);
 /* The same split into staging, the target and filter scores, and the dense count; any out pointer may be NULL. */
 ge_status ge_rank_last_phase_ms(const ge_rank *r, float *stage_ms, float *gather_ms, float *count_ms);
+/* *n = pairs; *candidates = V; *dim; *ranges = the candidate ranges the last run's grid had (0 before the first run: the
+ * results do not depend on it).  Any out pointer may be NULL. */
+ge_status ge_rank_get(const ge_rank *r, int64_t *n, int64_t *candidates, int32_t *dim, int32_t *ranges);
 int32_t   ge_rank_summary_size(void);
 void      ge_rank_destroy(ge_rank *r);     /* before the ge_glove it was created for */
 

@@ -17,8 +17,8 @@ i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
 def test_header_symbols_are_exported():
     header = open(os.path.join(REPO, "include", "geglove.h")).read()
     declared = set(re.findall(r"\b(ge_glove_rank_\w+|ge_rank_\w+)\s*\(", header))
-    assert declared == {"ge_glove_rank_create", "ge_glove_rank_run", "ge_rank_last_kernel_ms", "ge_rank_last_phase_ms", "ge_rank_summary_size",
-                        "ge_rank_destroy"}
+    assert declared == {"ge_glove_rank_create", "ge_glove_rank_run", "ge_rank_last_kernel_ms", "ge_rank_last_phase_ms", "ge_rank_get",
+                        "ge_rank_summary_size", "ge_rank_destroy"}
     L = capi.lib()
     for name in declared:
         assert name in capi.SYMBOLS and getattr(L, name) is not None
@@ -80,6 +80,7 @@ def test_limits_are_refused_without_a_device():
     assert L.ge_glove_rank_run(None, None, None, None) == ARG
     assert L.ge_rank_last_kernel_ms(None, C.byref(ms)) == ARG
     assert L.ge_rank_last_phase_ms(None, None, None, None) == ARG
+    assert L.ge_rank_get(None, None, None, None, None) == ARG
     L.ge_rank_destroy(None)                                           # harmless
 
 

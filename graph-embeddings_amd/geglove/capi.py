@@ -53,6 +53,8 @@ SYMBOLS = (
     "ge_glove_predict_create", "ge_glove_predict_run", "ge_predict_last_kernel_ms", "ge_predict_get", "ge_predict_destroy",
     "ge_fold_cfg_default", "ge_fold_cfg_size", "ge_glove_fold_create", "ge_glove_fold_run", "ge_fold_last_kernel_ms", "ge_fold_get",
     "ge_fold_destroy", "ge_foldin_mask",
+    "ge_ivf_cfg_default", "ge_ivf_cfg_size", "ge_ivf_create", "ge_glove_ivf_create", "ge_ivf_query_rows", "ge_ivf_query_vectors", "ge_ivf_get",
+    "ge_ivf_last_kernel_ms", "ge_ivf_destroy",
 )
 GE_FOLD_FOCUS, GE_FOLD_CONTEXT = 0, 1
 FOLD_SIDES = {"focus": GE_FOLD_FOCUS, "context": GE_FOLD_CONTEXT}
@@ -136,6 +138,11 @@ class NnCfg(C.Structure):
 
 class KmeansCfg(C.Structure):
     _fields_ = [("metric", C.c_int32), ("k", C.c_int32), ("seed", C.c_uint64), ("device", C.c_int32), ("stream", C.c_void_p)]
+
+
+class IvfCfg(C.Structure):
+    _fields_ = [("metric", C.c_int32), ("lists", C.c_int32), ("train_iterations", C.c_int32), ("seed", C.c_uint64),
+                ("centroids", C.POINTER(C.c_float)), ("device", C.c_int32), ("stream", C.c_void_p)]
 
 
 class SynthCfg(C.Structure):
@@ -269,6 +276,7 @@ def lib():
     _declare_kmeans(L)
     _declare_predict(L)
     _declare_fold(L)
+    _declare_ivf(L)
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int:      # default restype -> ge_status
@@ -1000,6 +1008,140 @@ class Clustering:
     def close(self):
         if self._h:
             lib().ge_kmeans_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _declare_ivf(L):
+    """The inverted-file section of include/geglove.h."""
+    vp, i32p, f32p = C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float)
+    L.ge_ivf_cfg_default.argtypes = [C.POINTER(IvfCfg)]; L.ge_ivf_cfg_default.restype = None
+    L.ge_ivf_cfg_size.argtypes = []; L.ge_ivf_cfg_size.restype = C.c_int32
+    if L.ge_ivf_cfg_size() != C.sizeof(IvfCfg):
+        raise ImportError("libgeglove.so was built from another revision of include/geglove.h (ge_ivf_cfg is %d bytes there, %d here): "
+                          "rebuild with `make -C graph-embeddings_amd/csrc`" % (L.ge_ivf_cfg_size(), C.sizeof(IvfCfg)))
+    L.ge_ivf_create.argtypes = [f32p, C.c_int64, C.c_int32, i32p, C.c_int64, C.POINTER(IvfCfg), C.POINTER(vp)]
+    L.ge_glove_ivf_create.argtypes = [vp, i32p, C.c_int64, C.POINTER(IvfCfg), C.POINTER(vp)]
+    L.ge_ivf_query_rows.argtypes = [vp, i32p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, i32p, f32p, i32p, i32p]
+    L.ge_ivf_query_vectors.argtypes = [vp, f32p, C.c_int64, C.c_int32, C.c_int32, i32p, f32p, i32p, i32p]
+    L.ge_ivf_get.argtypes = [vp, C.POINTER(C.c_int64), i32p, i32p, i32p, i32p, f32p, i32p, i32p]
+    L.ge_ivf_last_kernel_ms.argtypes = [vp, f32p, f32p, f32p, f32p]
+    L.ge_ivf_destroy.argtypes = [vp]; L.ge_ivf_destroy.restype = None
+
+
+class IvfNeighbors:
+    """A ge_ivf index: IvfNeighbors.create(rows, lists) / IvfNeighbors.create_glove(handle, lists), then query_rows(ids, k, nprobe) /
+    query_vectors(vectors, k, nprobe), each returning (int32[nq, k] original row ids, float32[nq, k] scores, int32[nq] counts,
+    int32[nq] candidates looked at), best first; slots past a count hold (-1, -inf)."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @staticmethod
+    def _cfg(lists, train_iterations, seed, centroids, dim, metric, device):
+        import numpy as np
+        cfg = IvfCfg(); lib().ge_ivf_cfg_default(C.byref(cfg))
+        cfg.metric, cfg.lists, cfg.seed, cfg.device = NN_METRICS.get(metric, metric), lists, seed & (2 ** 64 - 1), device
+        if train_iterations is not None:
+            cfg.train_iterations = train_iterations
+        keep = None
+        if centroids is not None:
+            keep = np.ascontiguousarray(centroids, dtype=np.float32)
+            if dim is not None and keep.shape != (lists, dim):
+                raise ValueError("centroids must be %d x %d, got %r" % (lists, dim, keep.shape))
+            cfg.centroids = keep.ctypes.data_as(C.POINTER(C.c_float))
+        return cfg, keep
+
+    @classmethod
+    def create(cls, rows, lists, subset=None, train_iterations=None, seed=0, centroids=None, metric="cosine", device=0):
+        import numpy as np
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        keep, sub, n_sub = Neighbors._subset(subset)
+        cfg, cen = cls._cfg(lists, train_iterations, seed, centroids, rows.shape[1], metric, device)
+        h = C.c_void_p()
+        check(lib().ge_ivf_create(rows.ctypes.data_as(C.POINTER(C.c_float)), rows.shape[0], rows.shape[1], sub, n_sub, C.byref(cfg), C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def create_glove(cls, glove_handle, lists, subset=None, train_iterations=None, seed=0, centroids=None, metric="cosine"):
+        keep, sub, n_sub = Neighbors._subset(subset)
+        cfg, cen = cls._cfg(lists, train_iterations, seed, centroids, None, metric, 0)
+        h = C.c_void_p()
+        check(lib().ge_glove_ivf_create(glove_handle, sub, n_sub, C.byref(cfg), C.byref(h)))
+        return cls(h)
+
+    def get(self):
+        """dict: n, dim, lists, train_steps, converged"""
+        n, dim, lists, steps, conv = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        check(lib().ge_ivf_get(self._h, C.byref(n), C.byref(dim), C.byref(lists), None, None, None, C.byref(steps), C.byref(conv)))
+        return {"n": n.value, "dim": dim.value, "lists": lists.value, "train_steps": steps.value, "converged": bool(conv.value)}
+
+    def _read(self, slot, shape, dtype, ctype):
+        import numpy as np
+        out = np.empty(shape, dtype=dtype)
+        args = [None] * 8
+        args[slot] = out.ctypes.data_as(C.POINTER(ctype))
+        check(lib().ge_ivf_get(self._h, *args))
+        return out
+
+    @property
+    def labels(self):
+        import numpy as np
+        return self._read(3, (self.get()["n"],), np.int32, C.c_int32)
+
+    @property
+    def sizes(self):
+        import numpy as np
+        return self._read(4, (self.get()["lists"],), np.int32, C.c_int32)
+
+    @property
+    def centroids(self):
+        import numpy as np
+        g = self.get()
+        return self._read(5, (g["lists"], g["dim"]), np.float32, C.c_float)
+
+    @staticmethod
+    def _out(nq, k):
+        import numpy as np
+        i32p = C.POINTER(C.c_int32)
+        idx = np.empty((nq, k), dtype=np.int32); score = np.empty((nq, k), dtype=np.float32)
+        count = np.empty(nq, dtype=np.int32); cand = np.empty(nq, dtype=np.int32)
+        return (idx, score, count, cand), (idx.ctypes.data_as(i32p), score.ctypes.data_as(C.POINTER(C.c_float)), count.ctypes.data_as(i32p),
+                                            cand.ctypes.data_as(i32p))
+
+    def query_rows(self, query_ids, k, nprobe, exclude_self=False):
+        """query_ids: None (every indexed row, in order) or row ids that are members of the index."""
+        import numpy as np
+        if query_ids is None:
+            ids, nq = None, self.get()["n"]
+        else:
+            keep = np.ascontiguousarray(query_ids, dtype=np.int32)
+            ids, nq = keep.ctypes.data_as(C.POINTER(C.c_int32)), keep.shape[0]
+        out, ptrs = self._out(nq, k)
+        check(lib().ge_ivf_query_rows(self._h, ids, nq, k, nprobe, 1 if exclude_self else 0, *ptrs))
+        return out
+
+    def query_vectors(self, vectors, k, nprobe):
+        import numpy as np
+        vectors = np.ascontiguousarray(vectors, dtype=np.float32)
+        out, ptrs = self._out(vectors.shape[0], k)
+        check(lib().ge_ivf_query_vectors(self._h, vectors.ctypes.data_as(C.POINTER(C.c_float)), vectors.shape[0], k, nprobe, *ptrs))
+        return out
+
+    def kernel_ms(self):
+        """(build, probe, scan, merge) device milliseconds: of creation, and of the last query call"""
+        v = [C.c_float() for _ in range(4)]
+        check(lib().ge_ivf_last_kernel_ms(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def close(self):
+        if self._h:
+            lib().ge_ivf_destroy(self._h)
             self._h = None
 
     def __del__(self):

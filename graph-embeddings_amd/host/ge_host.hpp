@@ -264,6 +264,10 @@ struct Configuration {
              std::string pca = "off";
              // K > 0: after the vectors, write the K nearest kept vertices of every kept vertex to <name>.neighbors.tsv; cosine | dot
              int neighbors = 0; std::string neighbors_metric = "cosine";
+             // L > 0 (needs neighbors, cosine): the neighbours come from an inverted-file index (ge_ivf_*) of L k-means lists trained
+             // with at most `neighbors_iterations` steps, `neighbors_probes` of them scanned per vertex; -1 = a value that is no
+             // integer >= 0, -2 = not set (probes: min(L, 16); iterations: 10)
+             long long neighbors_lists = 0, neighbors_probes = -2, neighbors_iterations = -2;
              // F > 0: hold out that share of the nonzeros (ge_holdout_mask), train on the rest, report the held-out mean cost after
              // every epoch and write <name>.holdout.tsv; held / total: the split's counts once the matrix is known (the banner shows them)
              double holdout = 0; long long holdout_held = -1, holdout_total = -1;
@@ -291,6 +295,9 @@ struct Configuration {
     bool usingPca() const { return pca.present; }
     bool applyingPca() const { return device.pca == "apply"; }
     bool writingNeighbors() const { return device.neighbors > 0; }
+    bool probingLists() const { return device.neighbors_lists > 0; }
+    long long neighborProbes() const { return device.neighbors_probes == -2 ? std::min<long long>(device.neighbors_lists, 16) : device.neighbors_probes; }
+    long long neighborIterations() const { return device.neighbors_iterations == -2 ? 10 : device.neighbors_iterations; }
     bool holdingOut() const { return device.holdout > 0; }
     bool ranking() const { return device.rank > 0; }
     bool clustering() const { return device.clusters > 0; }
@@ -397,6 +404,9 @@ struct Configuration {
                     else if (q.first == "pca") c.device.pca = q.second.scalar;
                     else if (q.first == "neighbors") c.device.neighbors = (int)num(&q.second);
                     else if (q.first == "neighbors_metric") c.device.neighbors_metric = q.second.scalar;
+                    else if (q.first == "neighbors_lists") c.device.neighbors_lists = whole_number(q.second);
+                    else if (q.first == "neighbors_probes") c.device.neighbors_probes = whole_number(q.second);
+                    else if (q.first == "neighbors_iterations") c.device.neighbors_iterations = whole_number(q.second);
                     else if (q.first == "holdout") c.device.holdout = whole_fraction(q.second);     // a number, all of it: anything else fails the check
                     else if (q.first == "rank") {                                               // an integer >= 0, all of it
                         const std::string &t = q.second.scalar;
@@ -468,6 +478,17 @@ struct Configuration {
         if (c.device.arith == "fp32" && c.device.mode != "stratified") throw InvalidConfigurationException("device.arith: fp32 needs device.mode: stratified");
         if (c.device.neighbors < 0 || c.device.neighbors > 128) throw InvalidConfigurationException("Invalid device.neighbors, choose a number from 1 to 128 (0 = off)");
         if (c.device.neighbors_metric != "cosine" && c.device.neighbors_metric != "dot") throw InvalidConfigurationException("Invalid device.neighbors_metric, choose one of: cosine, dot");
+        if (c.device.neighbors_lists < 0 || c.device.neighbors_lists > 65536)
+            throw InvalidConfigurationException("Invalid device.neighbors_lists, choose a number from 1 to 65536 (0 = off)");
+        if (!c.probingLists() && (c.device.neighbors_probes != -2 || c.device.neighbors_iterations != -2))
+            throw InvalidConfigurationException("device.neighbors_probes and device.neighbors_iterations need device.neighbors_lists");
+        if (c.probingLists() && !c.writingNeighbors()) throw InvalidConfigurationException("device.neighbors_lists needs device.neighbors");
+        if (c.probingLists() && c.device.neighbors_metric != "cosine")
+            throw InvalidConfigurationException("device.neighbors_lists needs device.neighbors_metric: cosine");
+        if (c.probingLists() && (c.neighborProbes() < 1 || c.neighborProbes() > std::min<long long>(c.device.neighbors_lists, 128)))
+            throw InvalidConfigurationException("Invalid device.neighbors_probes, choose a number from 1 to the smaller of device.neighbors_lists and 128");
+        if (c.probingLists() && (c.neighborIterations() < 0 || c.neighborIterations() > 1024))
+            throw InvalidConfigurationException("Invalid device.neighbors_iterations, choose a number from 0 to 1024");
         if (!(c.device.holdout >= 0 && c.device.holdout <= 0.5)) throw InvalidConfigurationException("Invalid device.holdout, choose a fraction from 0 to 0.5 (0 = off)");
         if (c.holdingOut() && c.device.gpus > 1) throw InvalidConfigurationException("device.holdout runs on one rank only, set device.gpus: 1");
         if (c.device.rank < 0) throw InvalidConfigurationException("Invalid device.rank, choose a number of held-out nonzeros to rank (0 = off)");
@@ -524,6 +545,8 @@ struct Configuration {
         if (device.mode == "stratified") L.push_back("Stratified trainer: " + (device.strata > 0 ? std::to_string(device.strata) + " strata" : std::string("strata chosen from the matrix")));
         if (device.arith == "fp32") L.push_back("Stratified arithmetic: fp32");
         if (writingNeighbors()) L.push_back("Nearest neighbours: " + std::to_string(device.neighbors) + " (" + device.neighbors_metric + ")");
+        if (probingLists()) L.push_back("Neighbour lists: " + std::to_string(device.neighbors_lists) + " (" + std::to_string(neighborProbes()) + " probed, at most " +
+                                        std::to_string(neighborIterations()) + " iterations)");
         if (holdingOut()) L.push_back("Holdout: " + java_number(device.holdout, false) + (device.holdout_total < 0 ? std::string() :
                                       " (" + std::to_string(device.holdout_held) + " of " + std::to_string(device.holdout_total) + " nonzeros)"));
         if (ranking()) L.push_back("Rank: " + std::to_string(device.rank) + " held-out nonzeros among all columns, training nonzeros filtered");
@@ -1526,7 +1549,8 @@ inline std::vector<int> keptVertices(const Configuration &config, const CoOccurr
 // on device.id, once -- also after a multi-GPU run (the result is replicated).  <fileName>.neighbors.tsv carries the banner, then
 // one line per kept vertex in dict order: its 0-based position in the dict file, then K pairs position<TAB>score, best first,
 // scores in the number format of the vectors file.  `warning` is set when fewer than K + 1 vertices are kept and K shrinks;
-// returns the line Main logs.
+// returns the line Main logs.  With `neighbors_lists: L` the lines come from an inverted-file index (ge_ivf_*) of min(L, kept)
+// lists, min(P, lists) of them probed: the same format, and a vertex whose probed lists hold fewer than K others lists what it has.
 inline std::string writeNeighbors(const Configuration &config, const Optimum &optimum, const CoOccurrenceMatrix &m, const std::string &fileName,
                                   const std::string &outputFolder, std::string &warning) {
     if (ge_nn_cfg_size() != (int32_t)sizeof(ge_nn_cfg))
@@ -1544,7 +1568,27 @@ inline std::string writeNeighbors(const Configuration &config, const Optimum &op
     }
     std::vector<int32_t> index((size_t)kept * (size_t)K);
     std::vector<float> score((size_t)kept * (size_t)K);
-    if (K > 0) {
+    std::vector<int32_t> count((size_t)kept, K);
+    std::string how;
+    if (K > 0 && config.probingLists()) {
+        if (ge_ivf_cfg_size() != (int32_t)sizeof(ge_ivf_cfg))
+            throw std::runtime_error("libgeglove.so and this host were built from different revisions of include/geglove.h; rebuild both");
+        std::vector<float> rows(optimum.result.begin(), optimum.result.end());      // widened fp32 values: exact
+        const std::vector<int32_t> subset(keep.begin(), keep.end());                // ascending by construction
+        ge_ivf_cfg cfg;
+        ge_ivf_cfg_default(&cfg);
+        cfg.lists = (int32_t)std::min<long long>(config.device.neighbors_lists, kept);
+        cfg.train_iterations = (int32_t)config.neighborIterations();
+        cfg.seed = (uint64_t)config.runSeed();
+        cfg.device = config.device.id;
+        const int32_t probes = (int32_t)std::min<long long>(config.neighborProbes(), cfg.lists);
+        ge_ivf *raw = nullptr;
+        check(ge_ivf_create(rows.data(), V, D, subset.data(), (int64_t)subset.size(), &cfg, &raw));
+        struct Del { void operator()(ge_ivf *p) const { ge_ivf_destroy(p); } };
+        std::unique_ptr<ge_ivf, Del> ivf(raw);
+        check(ge_ivf_query_rows(ivf.get(), nullptr, kept, K, probes, 1, index.data(), score.data(), count.data(), nullptr));
+        how = " from " + std::to_string(probes) + " of " + std::to_string(cfg.lists) + " lists";
+    } else if (K > 0) {
         std::vector<float> rows(optimum.result.begin(), optimum.result.end());      // widened fp32 values: exact
         const std::vector<int32_t> subset(keep.begin(), keep.end());                // ascending by construction
         ge_nn_cfg cfg;
@@ -1568,14 +1612,14 @@ inline std::string writeNeighbors(const Configuration &config, const Optimum &op
     char num[40];
     for (size_t k = 0; k < keep.size(); ++k) {
         line = std::to_string(k);
-        for (int j = 0; j < K; ++j) {
+        for (int j = 0; j < count[k]; ++j) {
             line += '\t'; line += std::to_string(position[(size_t)index[k * (size_t)K + (size_t)j]]);
             line += '\t'; line.append(num, (size_t)java_format_11_6E_to((double)score[k * (size_t)K + (size_t)j], num));
         }
         line += '\n';
         out.write(line.data(), (std::streamsize)line.size());
     }
-    return "wrote " + std::to_string(K) + " " + config.device.neighbors_metric + " neighbours of " + std::to_string(kept) + " vertices to " + outputFolder + "/" + file;
+    return "wrote " + std::to_string(K) + " " + config.device.neighbors_metric + " neighbours of " + std::to_string(kept) + " vertices to " + outputFolder + "/" + file + how;
 }
 
 // `device: { clusters: K }`: k-means over the kept vertices (the ones writeNeighbors lists), from the final result (after

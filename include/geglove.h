@@ -1032,6 +1032,83 @@ ge_status ge_fold_last_kernel_ms(const ge_fold *f, float *ms);
 ge_status ge_fold_get(const ge_fold *f, int64_t *n_rows, int64_t *nnz, int32_t *dim, int64_t *path);
 void      ge_fold_destroy(ge_fold *f);   /* before the ge_glove it was created for */
 
+/* ------------------------------------------------------------------------------------------
+ * Inverted-file index: top-k neighbours over the lists of the nprobe centroids closest to a query (IVF-flat), on one device.
+ * Approximate only in WHICH candidates are looked at; every score, the order and every byte that comes back are exact and a
+ * function of the input alone.  The reference has no counterpart, so these are product semantics.  The metric is cosine only:
+ * GE_NN_DOT is GE_ERR_ARG at creation ("no quantiser for dot").
+ *   indexed rows  exactly as ge_nn_create: host rows with an optional strictly ascending subset, or the vectors of a trainer
+ *                 handle (ge_glove_ivf_create, bit for bit the index built from ge_glove_extract_f32's output).  Position
+ *                 p = 0 .. n-1 is the p-th indexed row.  Rows are prepared as GE_NN_COSINE prepares them.
+ *   centroids     L = cfg.lists of them.  TRAINED (cfg.centroids == NULL): the keyed initial sample of ge_kmeans_* with cfg.seed,
+ *                 then cfg.train_iterations = T >= 0 steps of ge_kmeans_step, stopping early when a step changes no label; the
+ *                 centroids after the last update are the index's, bit for bit what ge_kmeans_create + ge_kmeans_run(T) +
+ *                 ge_kmeans_get(centroids) return for the same rows, GE_KM_COSINE, k = L and the same seed (the index calls that
+ *                 implementation; it does not restate it).  GIVEN (cfg.centroids != NULL): HOST float[L * dim], prepared like
+ *                 ge_kmeans_set_centroids prepares them; no training runs.  (Trained centroids are taken as ge_kmeans_get
+ *                 returns them, not prepared again: giving them back by value reproduces the index wherever preparing a
+ *                 prepared row returns its bits, which tests/test_ivf_ref.py asserts on the tables it uses.)
+ *   lists         label[p] = one k-means assign against the index's centroids: the score is the fp32 fmaf chain from 0.0f over
+ *                 ascending d, the winner the first c in the total order (score descending as fp32 compares, -0 = +0, NaN as
+ *                 -inf, equal scores by ascending c).  List c holds the positions with label == c in ascending p.  Empty lists
+ *                 are legal.
+ *   probe         a query (by row id: its prepared row; by value: prepared like a query vector of ge_nn_*) is scored against
+ *                 all L centroids with the same chain; its probed lists are the first nprobe centroids in that total order.
+ *   candidates    C_q = the union of the probed lists, minus the query's own position under exclude_self.
+ *   result        the first min(k, |C_q|) members of C_q in the total order of ge_nn_*: score descending, equal scores by
+ *                 ascending ORIGINAL row id.  The score is s(q, c) as ge_nn_* defines it: the bits the exact index returns for
+ *                 that pair.  out_count[q] = min(k, |C_q|); the remaining slots hold (-1, -inf); a real candidate whose score is
+ *                 -inf precedes the fill.  out_candidates[q] = |C_q|.
+ *   consequences  with nprobe == L the index and score arrays equal ge_nn_query_rows / ge_nn_query_vectors byte for byte.
+ *                 Results do not depend on batch, grid, tile or the order in which anything arrives; there are no floating-point
+ *                 atomics; the index is a pure read of a trainer handle.
+ * Limits, checked on the host before any device work (GE_ERR_ARG without a GPU): the limits of ge_nn_create on rows, dim and
+ * subset; 1 <= L <= min(n, 65536); 0 <= T <= 1024; 1 <= nprobe <= min(L, 128); 1 <= k <= 128; query ids that are members of the
+ * index; non-finite rows, centroids or query vectors ("non-finite input"; the rows of a trainer handle are looked at on the
+ * device); no null mandatory argument.  No device: GE_ERR_HIP.
+ * Device memory, until ge_ivf_destroy: the table in list order (n * D4 * 4 bytes, D4 = dim rounded up to 4), 4 n bytes of
+ * original row ids beside it, 4 (L + 1) bytes of list offsets and L * D4 * 4 bytes of centroids.  While ge_ivf_create runs: a
+ * second copy of the table in position order (and, when it trains, what ge_kmeans_* holds, before the index allocates).
+ * While a query call runs: the partial lists of a batch of queries (at most 2^24 entries of 8 bytes, or one tile of 64 queries
+ * where that needs more), 24 bytes per (query, probe) pair for the schedule, and the sort's scratch.  These are allocated and
+ * freed by every query call (about twenty allocations, nothing is cached between calls): a call with a handful of queries is
+ * dominated by them, so send queries in large sets.  The host keeps 8 n bytes (labels and where each position sits in the
+ * table).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct ge_ivf ge_ivf;
+typedef struct {
+    int32_t  metric;            /* GE_NN_COSINE; GE_NN_DOT is refused */
+    int32_t  lists;             /* L */
+    int32_t  train_iterations;  /* T: k-means steps at most, when centroids is NULL */
+    uint64_t seed;              /* of the k-means initial sample */
+    const float *centroids;     /* NULL (train) or HOST float[lists * dim] */
+    int32_t  device;            /* HIP device ordinal */
+    void    *stream;            /* hipStream_t or NULL */
+} ge_ivf_cfg;
+void      ge_ivf_cfg_default(ge_ivf_cfg *cfg);            /* cosine, lists 0 (must be set), T = 10, seed 0, train, device 0 */
+int32_t   ge_ivf_cfg_size(void);
+/* rows, subset: as ge_nn_create.  The index lives on the device until ge_ivf_destroy. */
+ge_status ge_ivf_create(const float *rows, int64_t n_rows, int32_t dim, const int32_t *subset, int64_t n_subset,
+                        const ge_ivf_cfg *cfg, ge_ivf **out);
+/* The same on the vectors a trainer handle holds; runs on the handle's device (cfg->device is ignored), writes no trainer table. */
+ge_status ge_glove_ivf_create(ge_glove *h, const int32_t *subset, int64_t n_subset, const ge_ivf_cfg *cfg, ge_ivf **out);
+/* query_ids: NULL (every indexed row, in order; n_queries must then be the number of indexed rows) or n_queries member ids.
+ * out_index, out_score: HOST [n_queries * k]; out_count, out_candidates: HOST int32[n_queries].  Any out pointer may be NULL. */
+ge_status ge_ivf_query_rows(ge_ivf *p, const int32_t *query_ids, int64_t n_queries, int32_t k, int32_t nprobe, int32_t exclude_self,
+                            int32_t *out_index, float *out_score, int32_t *out_count, int32_t *out_candidates);
+/* vectors: HOST float[n_queries * dim] */
+ge_status ge_ivf_query_vectors(ge_ivf *p, const float *vectors, int64_t n_queries, int32_t k, int32_t nprobe,
+                               int32_t *out_index, float *out_score, int32_t *out_count, int32_t *out_candidates);
+/* Any out pointer may be NULL.  labels: HOST int32[n], by position; sizes: HOST int32[L]; centroids: HOST float[L * dim];
+ * *train_steps, *converged: what ge_kmeans_run reported (0, 0 with given centroids or T = 0). */
+ge_status ge_ivf_get(const ge_ivf *p, int64_t *n, int32_t *dim, int32_t *lists, int32_t *labels, int32_t *sizes, float *centroids,
+                     int32_t *train_steps, int32_t *converged);
+/* Device time, hipEvents around the kernels, in milliseconds (0 = none ran); copies are not counted.  build: the index's own
+ * kernels at creation (prepare, assign, sort, gather; the k-means steps are ge_kmeans_*'s and not in it).  Of the last query
+ * call: probe (query preparation, centroid scores, the pair sort and the schedule), scan, merge.  Any out pointer may be NULL. */
+ge_status ge_ivf_last_kernel_ms(const ge_ivf *p, float *build_ms, float *probe_ms, float *scan_ms, float *merge_ms);
+void      ge_ivf_destroy(ge_ivf *p);
+
 /* ------------------------------------------------------------------------------------------ */
 const char *ge_last_error(void);     /* message of the calling thread's last failed call */
 const char *ge_version(void);

@@ -55,6 +55,9 @@ SYMBOLS = (
     "ge_fold_destroy", "ge_foldin_mask",
     "ge_ivf_cfg_default", "ge_ivf_cfg_size", "ge_ivf_create", "ge_glove_ivf_create", "ge_ivf_query_rows", "ge_ivf_query_vectors", "ge_ivf_get",
     "ge_ivf_last_kernel_ms", "ge_ivf_destroy",
+    "ge_classify_cfg_default", "ge_classify_cfg_size", "ge_classify_create", "ge_glove_classify_create", "ge_classify_set_weights",
+    "ge_classify_eval", "ge_classify_run", "ge_classify_predict", "ge_classify_score", "ge_classify_get", "ge_classify_last_kernel_ms",
+    "ge_classify_destroy",
 )
 GE_FOLD_FOCUS, GE_FOLD_CONTEXT = 0, 1
 FOLD_SIDES = {"focus": GE_FOLD_FOCUS, "context": GE_FOLD_CONTEXT}
@@ -64,6 +67,10 @@ NN_METRICS = {"cosine": GE_NN_COSINE, "dot": GE_NN_DOT}
 GE_KM_COSINE, GE_KM_EUCLID = 0, 1
 KM_METRICS = {"cosine": GE_KM_COSINE, "euclid": GE_KM_EUCLID}
 GE_KM_INIT_KEY = 0x4B4D45414E53
+GE_CLS_COSINE, GE_CLS_RAW = 0, 1
+CLS_NORMALIZE = {"cosine": GE_CLS_COSINE, "none": GE_CLS_RAW}
+GE_CLS_STOP_NONE, GE_CLS_STOP_GRADIENT, GE_CLS_STOP_MAXITER, GE_CLS_STOP_LINESEARCH = 0, 1, 2, 3
+CLS_STOPS = ("none", "gradient", "maxiter", "linesearch")
 
 
 class GloveCfg(C.Structure):
@@ -138,6 +145,16 @@ class NnCfg(C.Structure):
 
 class KmeansCfg(C.Structure):
     _fields_ = [("metric", C.c_int32), ("k", C.c_int32), ("seed", C.c_uint64), ("device", C.c_int32), ("stream", C.c_void_p)]
+
+
+class ClassifyCfg(C.Structure):
+    _fields_ = [("normalize", C.c_int32), ("classes", C.c_int32), ("l2", C.c_double), ("tolerance", C.c_double), ("device", C.c_int32),
+                ("stream", C.c_void_p)]
+
+
+class ClassifySummary(C.Structure):
+    _fields_ = [("count", C.c_int64), ("correct", C.c_int64), ("accuracy", C.c_double), ("macro_f1", C.c_double),
+                ("tp", C.POINTER(C.c_int64)), ("fp", C.POINTER(C.c_int64)), ("fn", C.POINTER(C.c_int64))]
 
 
 class IvfCfg(C.Structure):
@@ -277,6 +294,7 @@ def lib():
     _declare_predict(L)
     _declare_fold(L)
     _declare_ivf(L)
+    _declare_classify(L)
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int:      # default restype -> ge_status
@@ -1154,3 +1172,169 @@ class IvfNeighbors:
 def check(status):
     if status != GE_OK:
         raise GeError(status, lib().ge_last_error().decode(errors="replace"))
+
+
+def _declare_classify(L):
+    """The classification section of include/geglove.h."""
+    vp, i32p, i64p, f32p, f64p = C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_double)
+    u8p = C.POINTER(C.c_uint8)
+    L.ge_classify_cfg_default.argtypes = [C.POINTER(ClassifyCfg)]; L.ge_classify_cfg_default.restype = None
+    L.ge_classify_cfg_size.argtypes = []; L.ge_classify_cfg_size.restype = C.c_int32
+    if L.ge_classify_cfg_size() != C.sizeof(ClassifyCfg):
+        raise ImportError("libgeglove.so was built from another revision of include/geglove.h (ge_classify_cfg is %d bytes there, %d here): "
+                          "rebuild with `make -C graph-embeddings_amd/csrc`" % (L.ge_classify_cfg_size(), C.sizeof(ClassifyCfg)))
+    L.ge_classify_create.argtypes = [f32p, C.c_int64, C.c_int32, i32p, C.c_int64, i32p, u8p, C.POINTER(ClassifyCfg), C.POINTER(vp)]
+    L.ge_glove_classify_create.argtypes = [vp, i32p, C.c_int64, i32p, u8p, C.POINTER(ClassifyCfg), C.POINTER(vp)]
+    L.ge_classify_set_weights.argtypes = [vp, f32p]
+    L.ge_classify_eval.argtypes = [vp, f64p, f64p]
+    L.ge_classify_run.argtypes = [vp, C.c_int32, i32p, i32p]
+    L.ge_classify_predict.argtypes = [vp, i32p, f32p]
+    L.ge_classify_score.argtypes = [vp, u8p, C.POINTER(ClassifySummary), i64p]
+    L.ge_classify_get.argtypes = [vp, i64p, i32p, i32p, i64p, f32p, i32p, i32p, f64p, i64p]
+    L.ge_classify_last_kernel_ms.argtypes = [vp, f32p, f32p, f32p]
+    L.ge_classify_destroy.argtypes = [vp]; L.ge_classify_destroy.restype = None
+
+
+class Classifier:
+    """A ge_classifier handle: Classifier.create(rows, labels, classes) / Classifier.create_glove(handle, labels, classes),
+    optionally set_weights(values), then eval() -> (loss, gradient), run(max_iter) -> (iterations run, stop), predict() ->
+    (labels, probabilities) and score(mask) -> dict."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @staticmethod
+    def _cfg(classes, normalize, l2, tolerance, device):
+        cfg = ClassifyCfg(); lib().ge_classify_cfg_default(C.byref(cfg))
+        cfg.normalize, cfg.classes, cfg.device = CLS_NORMALIZE.get(normalize, normalize), classes, device
+        if l2 is not None:
+            cfg.l2 = l2
+        if tolerance is not None:
+            cfg.tolerance = tolerance
+        return cfg
+
+    @staticmethod
+    def _marks(labels, train):
+        import numpy as np
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        keep = [labels]
+        tp = None
+        if train is not None:
+            train = np.ascontiguousarray(train, dtype=np.uint8)
+            if train.shape != labels.shape:
+                raise ValueError("train must have one entry per label")
+            keep.append(train)
+            tp = train.ctypes.data_as(C.POINTER(C.c_uint8))
+        return keep, labels.ctypes.data_as(C.POINTER(C.c_int32)), tp
+
+    @classmethod
+    def create(cls, rows, labels, classes, train=None, subset=None, normalize="cosine", l2=None, tolerance=None, device=0):
+        import numpy as np
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        keep, sub, n_sub = Neighbors._subset(subset)
+        n = n_sub if sub is not None else rows.shape[0]
+        marks, lp, tp = cls._marks(labels, train)
+        if marks[0].shape != (n,):
+            raise ValueError("labels must have one entry per indexed row (%d), got %r" % (n, marks[0].shape))
+        h = C.c_void_p()
+        check(lib().ge_classify_create(rows.ctypes.data_as(C.POINTER(C.c_float)), rows.shape[0], rows.shape[1], sub, n_sub, lp, tp,
+                                       C.byref(cls._cfg(classes, normalize, l2, tolerance, device)), C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def create_glove(cls, glove_handle, labels, classes, train=None, subset=None, normalize="cosine", l2=None, tolerance=None):
+        keep, sub, n_sub = Neighbors._subset(subset)
+        marks, lp, tp = cls._marks(labels, train)
+        h = C.c_void_p()
+        check(lib().ge_glove_classify_create(glove_handle, sub, n_sub, lp, tp, C.byref(cls._cfg(classes, normalize, l2, tolerance, 0)),
+                                             C.byref(h)))
+        return cls(h)
+
+    def get(self):
+        """dict: n, dim, classes, n_train, iterations, stop, loss, evaluations"""
+        n, nt, ev = C.c_int64(), C.c_int64(), C.c_int64()
+        dim, classes, it, stop = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        loss = C.c_double()
+        check(lib().ge_classify_get(self._h, C.byref(n), C.byref(dim), C.byref(classes), C.byref(nt), None, C.byref(it), C.byref(stop),
+                                    C.byref(loss), C.byref(ev)))
+        return {"n": n.value, "dim": dim.value, "classes": classes.value, "n_train": nt.value, "iterations": it.value,
+                "stop": CLS_STOPS[stop.value], "loss": loss.value, "evaluations": ev.value}
+
+    @property
+    def weights(self):
+        """fp32 [classes][dim + 1]: (float) of the master copy; column dim is the bias"""
+        import numpy as np
+        g = self.get()
+        out = np.empty((g["classes"], g["dim"] + 1), dtype=np.float32)
+        check(lib().ge_classify_get(self._h, None, None, None, None, out.ctypes.data_as(C.POINTER(C.c_float)), None, None, None, None))
+        return out
+
+    def set_weights(self, weights):
+        import numpy as np
+        g = self.get()
+        weights = np.ascontiguousarray(weights, dtype=np.float32)
+        if weights.shape != (g["classes"], g["dim"] + 1):
+            raise ValueError("weights must be %d x %d, got %r" % (g["classes"], g["dim"] + 1, weights.shape))
+        check(lib().ge_classify_set_weights(self._h, weights.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def eval(self):
+        """(loss, gradient fp64 [classes][dim + 1]) at the current weights; the optimiser's state does not change"""
+        import numpy as np
+        g = self.get()
+        grad = np.empty((g["classes"], g["dim"] + 1), dtype=np.float64)
+        loss = C.c_double()
+        check(lib().ge_classify_eval(self._h, C.byref(loss), grad.ctypes.data_as(C.POINTER(C.c_double))))
+        return loss.value, grad
+
+    def run(self, max_iter=200):
+        """Up to max_iter L-BFGS iterations: (iterations run, stop reason)."""
+        it, stop = C.c_int32(), C.c_int32()
+        check(lib().ge_classify_run(self._h, max_iter, C.byref(it), C.byref(stop)))
+        return it.value, CLS_STOPS[stop.value]
+
+    def predict(self):
+        """(labels int32 [n], probabilities fp32 [n]) of every position"""
+        import numpy as np
+        n = self.get()["n"]
+        label, prob = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.float32)
+        check(lib().ge_classify_predict(self._h, label.ctypes.data_as(C.POINTER(C.c_int32)), prob.ctypes.data_as(C.POINTER(C.c_float))))
+        return label, prob
+
+    def score(self, mask=None, confusion=False):
+        """dict: count, correct, accuracy, macro_f1, tp, fp, fn (int64 [classes]) and, when asked for, confusion [true][predicted]"""
+        import numpy as np
+        g = self.get()
+        i64p = C.POINTER(C.c_int64)
+        tp, fp, fn = (np.zeros(g["classes"], dtype=np.int64) for _ in range(3))
+        s = ClassifySummary()
+        s.tp, s.fp, s.fn = (a.ctypes.data_as(i64p) for a in (tp, fp, fn))
+        mp = None
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.uint8)
+            if mask.shape != (g["n"],):
+                raise ValueError("mask must have %d entries, got %r" % (g["n"], mask.shape))
+            mp = mask.ctypes.data_as(C.POINTER(C.c_uint8))
+        conf = np.zeros((g["classes"], g["classes"]), dtype=np.int64) if confusion else None
+        check(lib().ge_classify_score(self._h, mp, C.byref(s), conf.ctypes.data_as(i64p) if confusion else None))
+        out = {"count": s.count, "correct": s.correct, "accuracy": s.accuracy, "macro_f1": s.macro_f1, "tp": tp, "fp": fp, "fn": fn}
+        if confusion:
+            out["confusion"] = conf
+        return out
+
+    @property
+    def kernel_ms(self):
+        """(logits, softmax, gradient) device milliseconds of the last evaluation"""
+        a, b, c = C.c_float(), C.c_float(), C.c_float()
+        check(lib().ge_classify_last_kernel_ms(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def close(self):
+        if self._h:
+            lib().ge_classify_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

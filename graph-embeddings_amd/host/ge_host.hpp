@@ -34,6 +34,7 @@
 #include <string>
 #include <thread>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "../../include/geglove.h"
@@ -283,7 +284,12 @@ struct Configuration {
              // F > 0: the vertices ge_foldin_mask(seed, V, F) names are late -- their rows are withheld from training and folded in
              // after the last epoch (ge_glove_fold_*, `foldin_epochs` epochs on the focus side), <name>.foldin.tsv lists them;
              // late / vertices: the split's counts once the matrix is known (the banner shows them)
-             double foldin = 0; long long foldin_epochs = 50, foldin_late = -1, foldin_vertices = -1; } device;
+             double foldin = 0; long long foldin_epochs = 50, foldin_late = -1, foldin_vertices = -1;
+             // a labels file (key<TAB>class): after the vectors, fit a softmax regression on the labelled kept vertices outside the
+             // test split (ge_classify_*), predict every kept vertex and write <name>.classes.tsv; `classify_test` of the labelled
+             // vertices are held back for the test figures; cosine | none; -1 = a value that is no integer >= 0
+             std::string classify; double classify_test = 0.2, classify_l2 = 1e-4; long long classify_iterations = 200;
+             std::string classify_normalize = "cosine"; } device;
     std::vector<std::string> ignored_keys;     // legacy keys of the shipped YAMLs that the bean does not know
 
     int getThreads() const {       // Configuration.java:71-73
@@ -303,6 +309,7 @@ struct Configuration {
     bool clustering() const { return device.clusters > 0; }
     bool predicting() const { return device.predict > 0; }
     bool foldingIn() const { return device.foldin > 0; }
+    bool classifying() const { return !device.classify.empty(); }
     // the whole scalar as a number, else NaN (which fails every range check)
     static double whole_fraction(const YNode &n) {
         const std::string &t = n.scalar;
@@ -422,6 +429,11 @@ struct Configuration {
                     else if (q.first == "predict") c.device.predict = whole_number(q.second);
                     else if (q.first == "foldin") c.device.foldin = whole_fraction(q.second);
                     else if (q.first == "foldin_epochs") c.device.foldin_epochs = whole_number(q.second);
+                    else if (q.first == "classify") c.device.classify = q.second.scalar;
+                    else if (q.first == "classify_test") c.device.classify_test = whole_fraction(q.second);
+                    else if (q.first == "classify_l2") c.device.classify_l2 = whole_fraction(q.second);
+                    else if (q.first == "classify_iterations") c.device.classify_iterations = whole_number(q.second);
+                    else if (q.first == "classify_normalize") c.device.classify_normalize = q.second.scalar;
                     else if (q.first == "exchange") c.device.exchange = q.second.scalar;        // overlap | sync
                     else if (q.first == "transport") c.device.transport = q.second.scalar;      // auto | rccl | host
                     else if (q.first == "wire") c.device.wire = q.second.scalar;                // bf16 | f32
@@ -503,6 +515,10 @@ struct Configuration {
         if (c.device.foldin_epochs < 1 || c.device.foldin_epochs > 1024) throw InvalidConfigurationException("Invalid device.foldin_epochs, choose a number from 1 to 1024");
         if (c.foldingIn() && c.holdingOut()) throw InvalidConfigurationException("device.foldin and device.holdout split the matrix differently, set one of them");
         if (c.foldingIn() && c.device.gpus > 1) throw InvalidConfigurationException("device.foldin runs on one rank only, set device.gpus: 1");
+        if (!(c.device.classify_test >= 0 && c.device.classify_test <= 0.9)) throw InvalidConfigurationException("Invalid device.classify_test, choose a fraction from 0 to 0.9");
+        if (!(c.device.classify_l2 >= 0 && c.device.classify_l2 <= std::numeric_limits<double>::max())) throw InvalidConfigurationException("Invalid device.classify_l2, choose a number from 0 up");
+        if (c.device.classify_iterations < 1) throw InvalidConfigurationException("Invalid device.classify_iterations, choose a number from 1 up");
+        if (c.device.classify_normalize != "cosine" && c.device.classify_normalize != "none") throw InvalidConfigurationException("Invalid device.classify_normalize, choose one of: cosine, none");
     }
 
     static std::string similarity_to_string(const std::map<std::string, std::string> &m) {     // SimilarityGroup.toString
@@ -556,6 +572,8 @@ struct Configuration {
         if (foldingIn()) L.push_back("Foldin: " + java_number(device.foldin, false) + ", " + std::to_string(device.foldin_epochs) + " epochs" +
                                      (device.foldin_vertices < 0 ? std::string() : " (" + std::to_string(device.foldin_late) + " of " +
                                                                                     std::to_string(device.foldin_vertices) + " vertices late)"));
+        if (classifying()) L.push_back("Classify: " + device.classify + " (test " + java_number(device.classify_test, false) + ", l2 " + java_number(device.classify_l2, false) +
+                                       ", " + device.classify_normalize + ", at most " + std::to_string(device.classify_iterations) + " iterations)");
         return L;
     }
 };
@@ -1681,6 +1699,128 @@ inline std::string writeClusters(const Configuration &config, const Optimum &opt
     }
     return "wrote " + std::to_string(K) + " " + config.device.clusters_metric + " clusters of " + std::to_string(kept) + " vertices after " +
            std::to_string(steps) + " iterations (" + (converged ? "converged" : "not converged") + ") to " + outputFolder + "/" + file;
+}
+
+// `device: { classify: labels.tsv }`: softmax regression over the kept vertices (the ones writeClusters labels), from the final result
+// (after `device.pca: apply`), on device.id, once -- also after a multi-GPU run.  The labels file has lines key<TAB>class (`#` lines
+// and empty lines are skipped); keys are those of <fileName>.dict.tsv; a key that appears twice is an error; keys that are unknown or
+// not written are counted in `warning`; class ids are the ranks of the class names (of the kept vertices) in ascending byte order.
+// The test split is ge_holdout_mask(seed, n_labelled, F) over the labelled kept vertices in dict order (F > 0.5: the complement of
+// the mask of 1 - F); the others train.  With F = 0, or when the mask takes none, the test figures are over the training set.
+// <fileName>.classes.tsv carries the banner, one line `# C<TAB>train<TAB>test<TAB>iterations<TAB>stop<TAB>loss<TAB>test_accuracy<TAB>
+// test_macro_f1` (doubles as %.17g), C lines `# id<TAB>name<TAB>tp<TAB>fp<TAB>fn` over the test split, then one line per kept vertex in
+// dict order: its 0-based position in the dict file, the predicted id, its probability in the number format of the vectors file,
+// train | test | -, and the true id or -.  Returns the line Main logs.
+inline std::string writeClasses(const Configuration &config, const Optimum &optimum, const CoOccurrenceMatrix &m, const std::string &fileName,
+                                const std::string &outputFolder, uint64_t seed, std::string &warning) {
+    if (ge_classify_cfg_size() != (int32_t)sizeof(ge_classify_cfg))
+        throw std::runtime_error("libgeglove.so and this host were built from different revisions of include/geglove.h; rebuild both");
+    const int V = m.vocabSize();
+    if (V < 1 || optimum.result.size() % (size_t)V != 0) throw std::runtime_error("classify: the result is not a table of V rows");
+    const int D = (int)(optimum.result.size() / (size_t)V);
+    const std::vector<int> keep = keptVertices(config, m);
+    const size_t kept = keep.size();
+    std::unordered_map<std::string, int32_t> position;                              // key of a kept vertex -> line of the dict file
+    std::unordered_set<std::string> known;                                          // every key of the graph
+    for (int i = 0; i < V; ++i) known.insert(m.getKey(i));
+    for (size_t k = 0; k < kept; ++k) position[m.getKey(keep[k])] = (int32_t)k;
+    std::ifstream in(config.device.classify);
+    if (!in) throw std::runtime_error("classify: cannot open the labels file " + config.device.classify);
+    std::vector<std::string> name(kept);                                            // class name of every kept vertex, empty = none
+    std::vector<char> has(kept, 0);
+    std::unordered_set<std::string> seen;
+    long long unknown = 0, unwritten = 0, line_no = 0;
+    std::string line;
+    while (std::getline(in, line)) {
+        ++line_no;
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty() || line[0] == '#') continue;
+        const size_t tab = line.find('\t');
+        if (tab == std::string::npos || tab == 0 || tab + 1 == line.size())
+            throw std::runtime_error("classify: line " + std::to_string(line_no) + " of " + config.device.classify + " is not key<TAB>class");
+        const std::string key = line.substr(0, tab);
+        if (!seen.insert(key).second) throw std::runtime_error("classify: the key " + key + " appears twice in " + config.device.classify);
+        const auto at = position.find(key);
+        if (at == position.end()) { if (known.count(key)) ++unwritten; else ++unknown; continue; }
+        name[(size_t)at->second] = line.substr(tab + 1);
+        has[(size_t)at->second] = 1;
+    }
+    if (unknown + unwritten > 0)
+        warning = std::to_string(unknown + unwritten) + " keys of " + config.device.classify + " are skipped: " + std::to_string(unknown) + " unknown, " +
+                  std::to_string(unwritten) + " not written";
+    std::vector<std::string> classes;
+    for (size_t k = 0; k < kept; ++k) if (has[k]) classes.push_back(name[k]);
+    std::sort(classes.begin(), classes.end());                                      // std::string compares bytes as unsigned
+    classes.erase(std::unique(classes.begin(), classes.end()), classes.end());
+    if (classes.size() < 2) throw std::runtime_error("classify: " + std::to_string(classes.size()) + " classes among the written vertices, at least 2 are needed");
+    const int C = (int)classes.size();
+    std::vector<int32_t> labels(kept, -1);
+    std::vector<size_t> labelled;
+    for (size_t k = 0; k < kept; ++k)
+        if (has[k]) {
+            labels[k] = (int32_t)(std::lower_bound(classes.begin(), classes.end(), name[k]) - classes.begin());
+            labelled.push_back(k);
+        }
+    const double F = config.device.classify_test;
+    std::vector<uint8_t> pick(labelled.size(), 0);
+    if (F > 0) {
+        check(ge_holdout_mask(seed, (int64_t)pick.size(), F <= 0.5 ? F : 1.0 - F, pick.data()));
+        if (F > 0.5) for (auto &b : pick) b = b ? 0 : 1;
+    }
+    std::vector<uint8_t> train(kept, 0), test(kept, 0);
+    long long n_train = 0, n_test = 0;
+    for (size_t t = 0; t < labelled.size(); ++t) {
+        if (pick[t]) { test[labelled[t]] = 1; ++n_test; } else { train[labelled[t]] = 1; ++n_train; }
+    }
+    std::vector<float> rows(optimum.result.begin(), optimum.result.end());          // widened fp32 values: exact
+    const std::vector<int32_t> subset(keep.begin(), keep.end());                    // ascending by construction
+    ge_classify_cfg cfg;
+    ge_classify_cfg_default(&cfg);
+    cfg.normalize = config.device.classify_normalize == "none" ? GE_CLS_RAW : GE_CLS_COSINE;
+    cfg.classes = C;
+    cfg.l2 = config.device.classify_l2;
+    cfg.device = config.device.id;
+    ge_classifier *raw = nullptr;
+    check(ge_classify_create(rows.data(), V, D, subset.data(), (int64_t)subset.size(), labels.data(), train.data(), &cfg, &raw));
+    struct Del { void operator()(ge_classifier *p) const { ge_classify_destroy(p); } };
+    std::unique_ptr<ge_classifier, Del> clf(raw);
+    int32_t stop = 0, iterations = 0;
+    double loss = 0.0;
+    check(ge_classify_run(clf.get(), (int32_t)config.device.classify_iterations, nullptr, &stop));
+    check(ge_classify_get(clf.get(), nullptr, nullptr, nullptr, nullptr, nullptr, &iterations, nullptr, &loss, nullptr));
+    std::vector<int32_t> predicted(kept);
+    std::vector<float> prob(kept);
+    check(ge_classify_predict(clf.get(), predicted.data(), prob.data()));
+    std::vector<int64_t> tp((size_t)C), fp((size_t)C), fn((size_t)C);
+    ge_classify_summary summary;
+    summary.tp = tp.data(); summary.fp = fp.data(); summary.fn = fn.data();
+    check(ge_classify_score(clf.get(), n_test > 0 ? test.data() : train.data(), &summary, nullptr));
+    static const char *stops[4] = {"none", "gradient", "maxiter", "linesearch"};
+    std::filesystem::create_directories(outputFolder);
+    const std::string file = fileName + ".classes.tsv";
+    std::ofstream out(outputFolder + "/" + file);
+    if (!out) throw std::runtime_error("cannot open " + file + " in " + outputFolder);
+    for (auto &l : config.banner()) out << "# " << l << "\n";
+    char head[200];
+    std::snprintf(head, sizeof head, "# %d\t%lld\t%lld\t%d\t%s\t%.17g\t%.17g\t%.17g\n", C, n_train, n_test, (int)iterations, stops[stop & 3], loss,
+                  summary.accuracy, summary.macro_f1);
+    out << head;
+    for (int c = 0; c < C; ++c)
+        out << "# " << c << "\t" << classes[(size_t)c] << "\t" << tp[(size_t)c] << "\t" << fp[(size_t)c] << "\t" << fn[(size_t)c] << "\n";
+    char num[40];
+    for (size_t k = 0; k < kept; ++k) {
+        line = std::to_string(k);
+        line += '\t'; line += std::to_string(predicted[k]);
+        line += '\t'; line.append(num, (size_t)java_format_11_6E_to((double)prob[k], num));
+        line += train[k] ? "\ttrain\t" : test[k] ? "\ttest\t" : "\t-\t";
+        line += labels[k] >= 0 ? std::to_string(labels[k]) : std::string("-");
+        line += '\n';
+        out.write(line.data(), (std::streamsize)line.size());
+    }
+    std::snprintf(head, sizeof head, "%.6g", summary.accuracy);
+    return "fitted " + std::to_string(C) + " classes on " + std::to_string(n_train) + " vertices in " + std::to_string(iterations) + " iterations (" +
+           stops[stop & 3] + "), " + (n_test > 0 ? "test" : "training") + " accuracy " + head + " over " + std::to_string(summary.count) + "; wrote " +
+           outputFolder + "/" + file;
 }
 
 // `device: { holdout: F }`: <fileName>.holdout.tsv carries the banner, then one line per epoch: the iteration as ge_glove_epoch

@@ -2,7 +2,8 @@
 // Same single flag, same settings banner, same output files ./out/<name>.{vectors,dict}.tsv
 // (and <name>.neighbors.tsv with `device: { neighbors: K }`, <name>.holdout.tsv with `device: { holdout: F }`,
 // <name>.rank.tsv with `device: { rank: Q }`, <name>.clusters.tsv with `device: { clusters: K }`,
-// <name>.links.tsv with `device: { predict: K }`, <name>.foldin.tsv with `device: { foldin: F }`).
+// <name>.links.tsv with `device: { predict: K }`, <name>.foldin.tsv with `device: { foldin: F }`,
+// <name>.classes.tsv with `device: { classify: labels.tsv }`).
 #include <ctime>
 #include "ge_host.hpp"
 
@@ -130,6 +131,12 @@ static void runProgram(const Configuration &given) {                        // J
         const std::string done = writeClusters(config, optimum, bca, outFileName, "out", (uint64_t)config.runSeed(), warning);
         if (!warning.empty()) log_warn("Clusters", warning);
         log_info("Clusters", done);
+    }
+    if (config.classifying()) {
+        std::string warning;
+        const std::string done = writeClasses(config, optimum, bca, outFileName, "out", (uint64_t)config.runSeed(), warning);
+        if (!warning.empty()) log_warn("Classify", warning);
+        log_info("Classify", done);
     }
     g_optimizer = nullptr;
 }

@@ -958,6 +958,120 @@ ge_status ge_kmeans_last_kernel_ms(const ge_kmeans *p, float *assign_ms, float *
 void      ge_kmeans_destroy(ge_kmeans *p);
 
 /* ------------------------------------------------------------------------------------------
+ * Classification: given labels for some vertices, what are the labels of the rest?  Multinomial logistic (softmax) regression
+ * over a table of vectors, on one device, fitted by L-BFGS.  The reference stops at the vectors file and has no counterpart,
+ * so these are product semantics.  Every byte that comes back is a function of the input alone.
+ *   indexed rows  as ge_kmeans_*: host rows with an optional strictly ascending subset, or the vectors of a trainer handle.
+ *                 Position p = 0 .. n-1 is the p-th indexed row.  labels[p] is a class id in [0, C) or -1 (unlabelled);
+ *                 train[p] is a uint8, train == NULL meaning every labelled position trains.  The training members are the
+ *                 positions with labels[p] >= 0 and train[p] != 0 in ascending p: n_T >= 1 of them, member t the t-th.  A class
+ *                 may have no member.
+ *   features      Dp = dim + 1.  The prepared row xh_p holds dim values prepared exactly as GE_KM_COSINE (GE_CLS_COSINE, the
+ *                 default) or GE_KM_EUCLID (GE_CLS_RAW) prepares them, then 1.0f at [dim], then zeros up to Dp4 = Dp rounded up
+ *                 to 4.
+ *   weights       W is fp32 [C][Dp], element [dim] the bias.  The master copy theta is fp64 on the host, W = (float)theta rounded
+ *                 to nearest; the start is all zeros.
+ *   logit         z(p, c) = the fp32 fmaf chain from +0.0f over ascending d of the Dp4 elements, s = fmaf(xh_p[d], W_c[d], s)
+ *                 (k_cls_logits on the fp32 matrix cores, which give exactly that chain): the bias is the chain's last live
+ *                 product.
+ *   exp, log      fp64, every operation an IEEE fp64 operation, unfused, rounded to nearest even.
+ *                 LN2HI = 6.93147180369123816490e-01, LN2LO = 1.90821492927058770002e-10.
+ *                 cexp(t), t <= 0:  0.0 if t < -708; else k = rint(t * 1.4426950408889634), r = (t - k*LN2HI) - k*LN2LO,
+ *                 p = 1/13!, then for j = 12 .. 0: p = p*r + 1/j! (each 1/j! the fp64 quotient 1.0 / (double)j!); ldexp(p, k).
+ *                 clog(S), S >= 1:  (f, k) = frexp(S); if f < 0.70710678118654752440 then f = 2f, k = k - 1;
+ *                 s = (f - 1)/(f + 1), w = s*s, q = 1/25, then for j = 23, 21, .. 1: q = q*w + 1/j (fp64 quotients);
+ *                 k*LN2HI + (k*LN2LO + (2*s)*q).  cexp is within 1 ulp of exp on [-708, 0], clog within 3 ulp of log on
+ *                 [1, 1024]; cexp(0) = 1.0, clog(1) = 0.0.
+ *   softmax       of a row: m = max_c z as fp32 compares; T_c = (double)z_c - (double)m; e_c = cexp(T_c); S = the fp64 sum of
+ *                 e_c from 0.0 over ascending c; q_c = e_c / S; pf_c = 0.0f if q_c < 2^-60, else (float)q_c.  For member t with
+ *                 label y: the row loss l_t = clog(S) - T_y and the residuals r[t][c] = pf_c - (c == y ? 1.0f : 0.0f), one fp32
+ *                 subtraction.  A non-finite logit: ge_classify_eval and ge_classify_predict fail with GE_ERR_STATE ("non-finite
+ *                 logit") and leave the handle unchanged; inside ge_classify_run it is a rejected trial.
+ *   loss          L = the fp64 sum of l_t over a fixed partition: blocks of 1024 members each summed from 0.0 in ascending t,
+ *                 then the blocks from 0.0 in ascending order.  reg = the fp64 sum from 0.0 over ascending (c, d < dim) of the
+ *                 unfused (double)W*(double)W.  f = L / (double)n_T + (0.5 * l2) * reg.
+ *   gradient      pieces of 1024 consecutive members.  Gp[piece][c][d] = the fp32 fmaf chain from +0.0f over the piece's
+ *                 members in ascending t of fmaf(r[t][c], xh_t[d], s) (k_cls_gradient on the fp32 matrix cores, the members
+ *                 along k).  G[c][d] = the fp64 sum from 0.0 of (double)Gp over ascending pieces.
+ *                 g[c*Dp + d] = G/(double)n_T + l2 * (double)W[c][d] for d < dim; the bias element is G/(double)n_T alone.
+ *                 No floating-point atomics anywhere.
+ *   optimiser     L-BFGS on the host in fp64, a history of 8 pairs.  dot(a, b) = the fp64 sum from 0.0 over ascending index of
+ *                 the unfused products.  State: theta, f, g, the history H (pairs s, y, sy, oldest first), it.
+ *                 1. max|g| <= tolerance: stop GRADIENT.  The call's max_iter iterations used up: stop MAXITER.
+ *                 2. q = g; newest to oldest: a_j = dot(s_j, q) / sy_j, q -= a_j * y_j; if H is not empty,
+ *                    q = (sy_new / dot(y_new, y_new)) * q; oldest to newest: b = dot(y_j, q) / sy_j, q += (a_j - b) * s_j;
+ *                    d = -q, dg = dot(d, g); if !(dg < 0): empty H, d = -g, dg = dot(d, g).
+ *                 3. alpha = 1.0 with history, else 1.0 / max(1.0, sqrt(dot(g, g))).  Up to 30 trials of theta' = theta + alpha*d,
+ *                    (f', g') = the loss and gradient at theta'; accept when f' <= f + (1e-4 * alpha) * dg (a NaN fails);
+ *                    otherwise alpha = 0.5 * alpha.  None accepted: with history, empty H and go back to 2 with the same it;
+ *                    without, stop LINESEARCH.
+ *                 4. s = theta' - theta, y = g' - g, sy = dot(s, y); keep the pair when sy > 1e-10 * dot(y, y), dropping the
+ *                    oldest beyond 8.  Take theta', f', g'; it += 1.
+ *                 The state survives between calls of ge_classify_run: run(a) then run(b) is run(a + b) unless the first stopped.
+ *   prediction    for every position: label[p] = the first class in the total order of ge_nn_* (z descending as fp32 compares,
+ *                 then the lower id); prob[p] = (float)(1.0 / S) (the best class has e = cexp(0) = 1.0).
+ *   score         over the labelled positions p with mask[p] != 0 (mask == NULL: every labelled position), prediction against
+ *                 label: integer tp, fp, fn per class and optionally the C x C confusion counts [true][predicted];
+ *                 accuracy = correct / count (0 when count is 0); F1_c = 2tp / (2tp + fp + fn) in fp64; macro_f1 = the fp64
+ *                 mean over ascending c of the F1_c of the classes with tp + fp + fn > 0 (0 when there is none).
+ * Limits, checked on the host before any device work (GE_ERR_ARG without a GPU): 2 <= C <= 1024; labels in [-1, C); n_T >= 1;
+ * n * C <= 2^33; l2 >= 0 and finite; tolerance >= 0; max_iter >= 1; finite weights; the limits of ge_kmeans_create on rows, dim
+ * and subset; no null mandatory argument.  Non-finite input rows: GE_ERR_ARG ("non-finite input").  No device: GE_ERR_HIP.
+ * Device memory: the prepared rows (n * Dp4 * 4 bytes), logits for max(n_T, min(n, 2^26 / C)) rows and residuals for n_T rows
+ * (C * 4 bytes each), 16 bytes per member, and ceil(n_T / 1024) * C * Dp4 * 4 bytes of piece gradients, until
+ * ge_classify_destroy.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct ge_classifier ge_classifier;
+enum { GE_CLS_COSINE = 0, GE_CLS_RAW = 1 };
+enum { GE_CLS_STOP_NONE = 0, GE_CLS_STOP_GRADIENT = 1, GE_CLS_STOP_MAXITER = 2, GE_CLS_STOP_LINESEARCH = 3 };
+typedef struct {
+    int32_t  normalize;      /* GE_CLS_COSINE or GE_CLS_RAW */
+    int32_t  classes;        /* C */
+    double   l2;             /* weight of the penalty on the non-bias weights */
+    double   tolerance;      /* on max|g| */
+    int32_t  device;         /* HIP device ordinal */
+    void    *stream;         /* hipStream_t or NULL */
+} ge_classify_cfg;
+typedef struct {
+    int64_t  count, correct; /* scored positions, and those predicted right */
+    double   accuracy, macro_f1;
+    int64_t *tp, *fp, *fn;   /* IN: each NULL or HOST int64[C] that receives the per-class counts */
+} ge_classify_summary;
+void      ge_classify_cfg_default(ge_classify_cfg *cfg);  /* cosine, classes 0 (must be set), l2 1e-4, tolerance 1e-4, device 0, null stream */
+int32_t   ge_classify_cfg_size(void);
+/* rows: HOST float[n_rows * dim], row-major; subset as ge_kmeans_create; labels: HOST int32[n]; train: NULL or HOST uint8[n]
+ * (n = the indexed rows).  The handle starts at zero weights and lives on the device until ge_classify_destroy. */
+ge_status ge_classify_create(const float *rows, int64_t n_rows, int32_t dim, const int32_t *subset, int64_t n_subset,
+                             const int32_t *labels, const uint8_t *train, const ge_classify_cfg *cfg, ge_classifier **out);
+/* The same on the vectors a trainer handle holds -- what ge_glove_extract_f32 returns -- without the trip through host memory;
+ * bit for bit the handle ge_classify_create builds from that output.  Runs on the trainer handle's device (cfg->device is
+ * ignored) and writes no trainer table. */
+ge_status ge_glove_classify_create(ge_glove *h, const int32_t *subset, int64_t n_subset, const int32_t *labels, const uint8_t *train,
+                                   const ge_classify_cfg *cfg, ge_classifier **out);
+/* weights: HOST float[C * Dp], finite.  theta = (double)weights.  Starts over: the history is emptied, iterations, evaluations
+ * and the stop reason are 0 again. */
+ge_status ge_classify_set_weights(ge_classifier *p, const float *weights);
+/* *loss = f and grad[C * Dp] = g at the current weights: a pure read, the optimiser's state does not change.  Either may be NULL. */
+ge_status ge_classify_eval(ge_classifier *p, double *loss, double *grad);
+/* Up to max_iter iterations from the current state.  *iterations = the iterations this call ran; *stop = GE_CLS_STOP_*.
+ * Either may be NULL. */
+ge_status ge_classify_run(ge_classifier *p, int32_t max_iter, int32_t *iterations, int32_t *stop);
+/* label: HOST int32[n], prob: HOST float[n], at the current weights.  Either may be NULL. */
+ge_status ge_classify_predict(ge_classifier *p, int32_t *label, float *prob);
+/* mask: NULL or HOST uint8[n]; confusion: NULL or HOST int64[C * C], [true][predicted].  Runs a prediction. */
+ge_status ge_classify_score(ge_classifier *p, const uint8_t *mask, ge_classify_summary *summary, int64_t *confusion);
+/* Any out pointer may be NULL.  weights: HOST float[C * Dp] = (float)theta; *iterations: since creation or
+ * ge_classify_set_weights; *stop: of the last run (0 before it); *loss: f at theta (0 before the first run); *evaluations: the
+ * loss-and-gradient evaluations ge_classify_run has made since creation or ge_classify_set_weights, the one at the starting
+ * point and rejected trials included. */
+ge_status ge_classify_get(const ge_classifier *p, int64_t *n, int32_t *dim, int32_t *classes, int64_t *n_train, float *weights,
+                          int32_t *iterations, int32_t *stop, double *loss, int64_t *evaluations);
+/* Device time of the last evaluation's logits, softmax (the loss block sums included) and gradient (the piece sums included),
+ * hipEvents around the kernels, in milliseconds (0 = none ran); copies are not counted.  Any out pointer may be NULL. */
+ge_status ge_classify_last_kernel_ms(const ge_classifier *p, float *logits_ms, float *softmax_ms, float *gradient_ms);
+void      ge_classify_destroy(ge_classifier *p);
+
+/* ------------------------------------------------------------------------------------------
  * Fold-in: a vector for a vertex that arrives after training.  A new row is a list of entries (id, x) against the trained
  * rows of the other side; it is fitted by the AdaGrad update of GE_ARITH_FP32 with that other side held constant.  The
  * reference has no counterpart, so these are product semantics.

@@ -58,6 +58,8 @@ SYMBOLS = (
     "ge_classify_cfg_default", "ge_classify_cfg_size", "ge_classify_create", "ge_glove_classify_create", "ge_classify_set_weights",
     "ge_classify_eval", "ge_classify_run", "ge_classify_predict", "ge_classify_score", "ge_classify_get", "ge_classify_last_kernel_ms",
     "ge_classify_destroy",
+    "ge_match_cfg_default", "ge_match_cfg_size", "ge_match_summary_size", "ge_match_create", "ge_glove_match_create", "ge_match_run",
+    "ge_match_get", "ge_match_last_kernel_ms", "ge_match_destroy",
 )
 GE_FOLD_FOCUS, GE_FOLD_CONTEXT = 0, 1
 FOLD_SIDES = {"focus": GE_FOLD_FOCUS, "context": GE_FOLD_CONTEXT}
@@ -160,6 +162,14 @@ class ClassifySummary(C.Structure):
 class IvfCfg(C.Structure):
     _fields_ = [("metric", C.c_int32), ("lists", C.c_int32), ("train_iterations", C.c_int32), ("seed", C.c_uint64),
                 ("centroids", C.POINTER(C.c_float)), ("device", C.c_int32), ("stream", C.c_void_p)]
+
+
+class MatchCfg(C.Structure):
+    _fields_ = [("metric", C.c_int32), ("device", C.c_int32), ("stream", C.c_void_p)]
+
+
+class MatchSummary(C.Structure):
+    _fields_ = [("pairs", C.c_int64), ("components", C.c_int64), ("groups", C.c_int64), ("grouped_rows", C.c_int64), ("largest", C.c_int64)]
 
 
 class SynthCfg(C.Structure):
@@ -295,6 +305,7 @@ def lib():
     _declare_fold(L)
     _declare_ivf(L)
     _declare_classify(L)
+    _declare_match(L)
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int:      # default restype -> ge_status
@@ -1160,6 +1171,95 @@ class IvfNeighbors:
     def close(self):
         if self._h:
             lib().ge_ivf_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _declare_match(L):
+    """The matching section of include/geglove.h."""
+    vp, i32p, f32p, i64p = C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_int64)
+    L.ge_match_cfg_default.argtypes = [C.POINTER(MatchCfg)]; L.ge_match_cfg_default.restype = None
+    L.ge_match_cfg_size.argtypes = []; L.ge_match_cfg_size.restype = C.c_int32
+    L.ge_match_summary_size.argtypes = []; L.ge_match_summary_size.restype = C.c_int32
+    if L.ge_match_cfg_size() != C.sizeof(MatchCfg) or L.ge_match_summary_size() != C.sizeof(MatchSummary):
+        raise ImportError("libgeglove.so was built from another revision of include/geglove.h (ge_match_cfg is %d bytes there, %d here; "
+                          "ge_match_summary %d there, %d here): rebuild with `make -C graph-embeddings_amd/csrc`"
+                          % (L.ge_match_cfg_size(), C.sizeof(MatchCfg), L.ge_match_summary_size(), C.sizeof(MatchSummary)))
+    L.ge_match_create.argtypes = [f32p, C.c_int64, C.c_int32, i32p, C.c_int64, C.POINTER(MatchCfg), C.POINTER(vp)]
+    L.ge_glove_match_create.argtypes = [vp, i32p, C.c_int64, C.POINTER(MatchCfg), C.POINTER(vp)]
+    L.ge_match_run.argtypes = [vp, C.c_float, C.c_int64]
+    L.ge_match_get.argtypes = [vp, i64p, i64p, C.POINTER(i32p), C.POINTER(i32p), C.POINTER(f32p), C.POINTER(i32p), C.POINTER(MatchSummary)]
+    L.ge_match_last_kernel_ms.argtypes = [vp, f32p, f32p, f32p, f32p]
+    L.ge_match_destroy.argtypes = [vp]; L.ge_match_destroy.restype = None
+
+
+class Matching:
+    """A ge_match index: Matching.from_rows(rows) / Matching.from_glove(handle), then run(threshold, max_pairs) ->
+    (int32[m] a, int32[m] b, float32[m] score, int32[n] label, summary dict): every pair a < b of original row ids whose score
+    reaches the threshold, in ascending (a, b), and per indexed position the smallest row id of its connected component.
+    More than max_pairs pairs: GeError with status GE_ERR_OVERFLOW; found() then gives the exact number."""
+
+    def __init__(self, handle, stream=None):
+        self._h = handle
+        self._stream = stream
+
+    @staticmethod
+    def _cfg(metric, device, stream):
+        cfg = MatchCfg(); lib().ge_match_cfg_default(C.byref(cfg))
+        cfg.metric, cfg.device, cfg.stream = NN_METRICS.get(metric, metric), device, stream
+        return cfg
+
+    @classmethod
+    def from_rows(cls, rows, subset=None, metric="cosine", device=0, stream=None):
+        import numpy as np
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        keep, sub, n_sub = Neighbors._subset(subset)
+        h = C.c_void_p()
+        check(lib().ge_match_create(rows.ctypes.data_as(C.POINTER(C.c_float)), rows.shape[0], rows.shape[1], sub, n_sub,
+                                    C.byref(cls._cfg(metric, device, stream)), C.byref(h)))
+        return cls(h, stream)
+
+    @classmethod
+    def from_glove(cls, glove_handle, subset=None, metric="cosine", stream=None):
+        keep, sub, n_sub = Neighbors._subset(subset)
+        h = C.c_void_p()
+        check(lib().ge_glove_match_create(glove_handle, sub, n_sub, C.byref(cls._cfg(metric, 0, stream)), C.byref(h)))
+        return cls(h, stream)
+
+    def found(self):
+        """The qualifying pairs of the last run, also after an overflow."""
+        n = C.c_int64()
+        check(lib().ge_match_get(self._h, None, C.byref(n), None, None, None, None, None))
+        return n.value
+
+    def run(self, threshold, max_pairs=1 << 24):
+        import numpy as np
+        check(lib().ge_match_run(self._h, threshold, max_pairs))
+        i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        n, a, b, score, label, summary = C.c_int64(), i32p(), i32p(), f32p(), i32p(), MatchSummary()
+        check(lib().ge_match_get(self._h, C.byref(n), None, C.byref(a), C.byref(b), C.byref(score), C.byref(label), C.byref(summary)))
+        m = summary.pairs
+
+        def copy(ptr, count, dtype):          # the views are the handle's: copy them out
+            return np.ctypeslib.as_array(ptr, shape=(count,)).astype(dtype, copy=True) if count else np.empty(0, dtype)
+
+        return (copy(a, m, np.int32), copy(b, m, np.int32), copy(score, m, np.float32), copy(label, n.value, np.int32),
+                {k: getattr(summary, k) for k, _ in MatchSummary._fields_})
+
+    def kernel_ms(self):
+        """(prepare, join, sort, components) device milliseconds: of creation, and of the last run"""
+        v = [C.c_float() for _ in range(4)]
+        check(lib().ge_match_last_kernel_ms(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def close(self):
+        if self._h:
+            lib().ge_match_destroy(self._h)
             self._h = None
 
     def __del__(self):

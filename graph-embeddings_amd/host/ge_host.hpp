@@ -289,7 +289,12 @@ struct Configuration {
              // test split (ge_classify_*), predict every kept vertex and write <name>.classes.tsv; `classify_test` of the labelled
              // vertices are held back for the test figures; cosine | none; -1 = a value that is no integer >= 0
              std::string classify; double classify_test = 0.2, classify_l2 = 1e-4; long long classify_iterations = 200;
-             std::string classify_normalize = "cosine"; } device;
+             std::string classify_normalize = "cosine";
+             // match: T -- after the vectors, list every pair of kept vertices whose score reaches T (ge_match_*) in <name>.matches.tsv
+             // and the groups those pairs connect in <name>.entities.tsv; cosine | dot; at most `match_max_pairs` pairs (2^24);
+             // an absent key is off; match is NaN for a value that is no finite number, match_max_pairs -1 for one that is no
+             // integer >= 0, -2 = not set
+             bool has_match = false; double match = 0; std::string match_metric; long long match_max_pairs = -2; } device;
     std::vector<std::string> ignored_keys;     // legacy keys of the shipped YAMLs that the bean does not know
 
     int getThreads() const {       // Configuration.java:71-73
@@ -310,6 +315,9 @@ struct Configuration {
     bool predicting() const { return device.predict > 0; }
     bool foldingIn() const { return device.foldin > 0; }
     bool classifying() const { return !device.classify.empty(); }
+    bool matching() const { return device.has_match; }
+    std::string matchMetric() const { return device.match_metric.empty() ? "cosine" : device.match_metric; }
+    long long matchMaxPairs() const { return device.match_max_pairs == -2 ? (1LL << 24) : device.match_max_pairs; }
     // the whole scalar as a number, else NaN (which fails every range check)
     static double whole_fraction(const YNode &n) {
         const std::string &t = n.scalar;
@@ -434,6 +442,9 @@ struct Configuration {
                     else if (q.first == "classify_l2") c.device.classify_l2 = whole_fraction(q.second);
                     else if (q.first == "classify_iterations") c.device.classify_iterations = whole_number(q.second);
                     else if (q.first == "classify_normalize") c.device.classify_normalize = q.second.scalar;
+                    else if (q.first == "match") { c.device.has_match = true; c.device.match = whole_fraction(q.second); }
+                    else if (q.first == "match_metric") c.device.match_metric = q.second.kind == YNode::Scalar && !q.second.scalar.empty() ? q.second.scalar : "?";
+                    else if (q.first == "match_max_pairs") c.device.match_max_pairs = whole_number(q.second);
                     else if (q.first == "exchange") c.device.exchange = q.second.scalar;        // overlap | sync
                     else if (q.first == "transport") c.device.transport = q.second.scalar;      // auto | rccl | host
                     else if (q.first == "wire") c.device.wire = q.second.scalar;                // bf16 | f32
@@ -519,6 +530,13 @@ struct Configuration {
         if (!(c.device.classify_l2 >= 0 && c.device.classify_l2 <= std::numeric_limits<double>::max())) throw InvalidConfigurationException("Invalid device.classify_l2, choose a number from 0 up");
         if (c.device.classify_iterations < 1) throw InvalidConfigurationException("Invalid device.classify_iterations, choose a number from 1 up");
         if (c.device.classify_normalize != "cosine" && c.device.classify_normalize != "none") throw InvalidConfigurationException("Invalid device.classify_normalize, choose one of: cosine, none");
+        if (!c.matching() && (!c.device.match_metric.empty() || c.device.match_max_pairs != -2))
+            throw InvalidConfigurationException("device.match_metric and device.match_max_pairs need device.match");
+        if (c.matching() && !(std::fabs(c.device.match) <= (double)std::numeric_limits<float>::max()))     // the library takes it as fp32
+            throw InvalidConfigurationException("Invalid device.match, choose a finite score threshold");
+        if (c.matching() && c.matchMetric() != "cosine" && c.matchMetric() != "dot") throw InvalidConfigurationException("Invalid device.match_metric, choose one of: cosine, dot");
+        if (c.matching() && (c.matchMaxPairs() < 1 || c.matchMaxPairs() > (1LL << 28)))
+            throw InvalidConfigurationException("Invalid device.match_max_pairs, choose a number from 1 to 268435456");
     }
 
     static std::string similarity_to_string(const std::map<std::string, std::string> &m) {     // SimilarityGroup.toString
@@ -574,6 +592,8 @@ struct Configuration {
                                                                                     std::to_string(device.foldin_vertices) + " vertices late)"));
         if (classifying()) L.push_back("Classify: " + device.classify + " (test " + java_number(device.classify_test, false) + ", l2 " + java_number(device.classify_l2, false) +
                                        ", " + device.classify_normalize + ", at most " + std::to_string(device.classify_iterations) + " iterations)");
+        if (matching()) L.push_back("Match: pairs scoring at least " + java_number(device.match, false) + " (" + matchMetric() + ", at most " +
+                                    std::to_string(matchMaxPairs()) + " pairs)");
         return L;
     }
 };
@@ -1821,6 +1841,89 @@ inline std::string writeClasses(const Configuration &config, const Optimum &opti
     return "fitted " + std::to_string(C) + " classes on " + std::to_string(n_train) + " vertices in " + std::to_string(iterations) + " iterations (" +
            stops[stop & 3] + "), " + (n_test > 0 ? "test" : "training") + " accuracy " + head + " over " + std::to_string(summary.count) + "; wrote " +
            outputFolder + "/" + file;
+}
+
+// `device: { match: T }`: every pair of kept vertices (the ones writeNeighbors lists) whose score reaches T and the groups those pairs
+// connect (ge_match_*), from the final result (after `device.pca: apply`), on device.id, once -- also after a multi-GPU run.
+// <fileName>.matches.tsv carries the banner, then one line keyA<TAB>keyB<TAB>score per pair in ascending (a, b) order of the vertex
+// ids (the order of the dict file), scores in the number format of the vectors file.  <fileName>.entities.tsv carries the banner,
+// then one line per component of at least two vertices in ascending label (its smallest vertex id): the members' keys in ascending
+// id, separated by tabs.  Keys are written as the dict file writes them.  More than `match_max_pairs` qualifying pairs is a
+// run-time error that names the number found and the key to raise; neither file is written then.  Returns the line Main logs.
+inline std::string writeMatches(const Configuration &config, const Optimum &optimum, const CoOccurrenceMatrix &m, const std::string &fileName,
+                                const std::string &outputFolder) {
+    if (ge_match_cfg_size() != (int32_t)sizeof(ge_match_cfg) || ge_match_summary_size() != (int32_t)sizeof(ge_match_summary))
+        throw std::runtime_error("libgeglove.so and this host were built from different revisions of include/geglove.h; rebuild both");
+    const int V = m.vocabSize();
+    if (V < 1 || optimum.result.size() % (size_t)V != 0) throw std::runtime_error("match: the result is not a table of V rows");
+    const int D = (int)(optimum.result.size() / (size_t)V);
+    const std::vector<int> keep = keptVertices(config, m);
+    const size_t kept = keep.size();
+    int64_t pairs = 0;
+    const int32_t *a = nullptr, *b = nullptr, *label = nullptr;
+    const float *score = nullptr;
+    ge_match_summary summary{};
+    struct Del { void operator()(ge_match *p) const { ge_match_destroy(p); } };
+    std::unique_ptr<ge_match, Del> match;
+    if (kept > 0) {
+        std::vector<float> rows(optimum.result.begin(), optimum.result.end());      // widened fp32 values: exact
+        const std::vector<int32_t> subset(keep.begin(), keep.end());                // ascending by construction
+        ge_match_cfg cfg;
+        ge_match_cfg_default(&cfg);
+        cfg.metric = config.matchMetric() == "dot" ? GE_NN_DOT : GE_NN_COSINE;
+        cfg.device = config.device.id;
+        ge_match *raw = nullptr;
+        check(ge_match_create(rows.data(), V, D, subset.data(), (int64_t)subset.size(), &cfg, &raw));
+        match.reset(raw);
+        const ge_status st = ge_match_run(raw, (float)config.device.match, (int64_t)config.matchMaxPairs());
+        if (st == GE_ERR_OVERFLOW) {
+            int64_t found = 0;
+            check(ge_match_get(raw, nullptr, &found, nullptr, nullptr, nullptr, nullptr, nullptr));
+            throw std::runtime_error("match: " + std::to_string(found) + " pairs reach device.match: " + java_number(config.device.match, false) +
+                                     ", more than device.match_max_pairs: " + std::to_string(config.matchMaxPairs()) +
+                                     "; raise device.match or device.match_max_pairs");
+        }
+        check(st);
+        check(ge_match_get(raw, nullptr, nullptr, &a, &b, &score, &label, &summary));
+        pairs = summary.pairs;
+    }
+    auto clean = [&](int vertex) {                                                  // a key as the dict file writes it
+        std::string out;
+        for (char ch : m.getKey(vertex)) if (ch != '\n' && ch != '\r' && ch != '\t') out.push_back(ch);
+        return out;
+    };
+    std::filesystem::create_directories(outputFolder);
+    const std::string file = fileName + ".matches.tsv", groups = fileName + ".entities.tsv";
+    std::ofstream out(outputFolder + "/" + file), ent(outputFolder + "/" + groups);
+    if (!out || !ent) throw std::runtime_error("cannot open " + file + " or " + groups + " in " + outputFolder);
+    for (auto &l : config.banner()) { out << "# " << l << "\n"; ent << "# " << l << "\n"; }
+    std::string line;
+    char num[40];
+    for (int64_t k = 0; k < pairs; ++k) {
+        line = clean(a[k]);
+        line += '\t'; line += clean(b[k]);
+        line += '\t'; line.append(num, (size_t)java_format_11_6E_to((double)score[k], num));
+        line += '\n';
+        out.write(line.data(), (std::streamsize)line.size());
+    }
+    // members by label: positions ascend with the vertex id, so a stable order by label lists every component in ascending id
+    std::vector<size_t> order;
+    for (size_t k = 0; k < kept; ++k) order.push_back(k);
+    std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return label[x] < label[y]; });
+    for (size_t at = 0; at < kept;) {
+        size_t end = at + 1;
+        while (end < kept && label[order[end]] == label[order[at]]) ++end;
+        if (end - at >= 2) {
+            line.clear();
+            for (size_t k = at; k < end; ++k) { if (k > at) line += '\t'; line += clean(keep[order[k]]); }
+            line += '\n';
+            ent.write(line.data(), (std::streamsize)line.size());
+        }
+        at = end;
+    }
+    return "matched " + std::to_string(pairs) + " " + config.matchMetric() + " pairs scoring at least " + java_number(config.device.match, false) + " among " +
+           std::to_string(kept) + " vertices: " + std::to_string(summary.groups) + " entities of " + std::to_string(summary.grouped_rows) + " vertices, the largest of " +
+           std::to_string(summary.largest) + "; wrote " + outputFolder + "/" + file + " and " + outputFolder + "/" + groups;
 }
 
 // `device: { holdout: F }`: <fileName>.holdout.tsv carries the banner, then one line per epoch: the iteration as ge_glove_epoch

@@ -3,7 +3,8 @@
 // (and <name>.neighbors.tsv with `device: { neighbors: K }`, <name>.holdout.tsv with `device: { holdout: F }`,
 // <name>.rank.tsv with `device: { rank: Q }`, <name>.clusters.tsv with `device: { clusters: K }`,
 // <name>.links.tsv with `device: { predict: K }`, <name>.foldin.tsv with `device: { foldin: F }`,
-// <name>.classes.tsv with `device: { classify: labels.tsv }`).
+// <name>.classes.tsv with `device: { classify: labels.tsv }`,
+// <name>.matches.tsv and <name>.entities.tsv with `device: { match: T }`).
 #include <ctime>
 #include "ge_host.hpp"
 
@@ -138,6 +139,7 @@ static void runProgram(const Configuration &given) {                        // J
         if (!warning.empty()) log_warn("Classify", warning);
         log_info("Classify", done);
     }
+    if (config.matching()) log_info("Match", writeMatches(config, optimum, bca, outFileName, "out"));
     g_optimizer = nullptr;
 }
 

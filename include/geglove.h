@@ -1223,8 +1223,70 @@ ge_status ge_ivf_get(const ge_ivf *p, int64_t *n, int32_t *dim, int32_t *lists, 
 ge_status ge_ivf_last_kernel_ms(const ge_ivf *p, float *build_ms, float *probe_ms, float *scan_ms, float *merge_ms);
 void      ge_ivf_destroy(ge_ivf *p);
 
+/* ------------------------------------------------------------------------------------------
+ * Matching: which rows are the same thing?  Every pair of indexed rows whose score reaches a threshold, and the groups those
+ * pairs connect, on one device.  No k is chosen in advance and no number of groups.  The reference draws such edges between
+ * literals at ingest (CompareJob); on the vectors it has no counterpart, so these are product semantics.
+ *   indexed rows  exactly as ge_nn_create: host rows with an optional strictly ascending subset, or the vectors of a trainer
+ *                 handle (ge_glove_match_create, bit for bit the index built from ge_glove_extract_f32's output).  Position
+ *                 p = 0 .. n-1 is the p-th indexed row.  Prepared row as ge_nn_*: COSINE: n = sqrt(sum_d x_d^2), accumulated in
+ *                 fp64 in ascending d; xh_d = (float)((double)x_d / n), rounded once; a zero row stays zero.  DOT: xh = x.
+ *   score         s(a, b) = sum_d xh_a[d] * xh_b[d], an fp32 fmaf chain from +0 in ascending d (k_match_join on the fp32 matrix
+ *                 cores): the bits ge_nn_* returns for that pair.  s(a, b) = s(b, a) bit for bit, because the products commute
+ *                 and the order of the sum is the same.  A sum that overflows to NaN counts as -inf: it reaches no threshold.
+ *   pairs         ge_match_run(p, threshold, max_pairs): all pairs of indexed rows a < b (ORIGINAL row ids) with
+ *                 s(a, b) >= threshold as fp32 compares them (so -0 = +0).  A row is never paired with itself, and a pair is
+ *                 listed once.  They come in ascending (a, b), each with its score bits.
+ *   overflow      more than max_pairs qualifying pairs: GE_ERR_OVERFLOW.  The handle then holds no pairs and no groups;
+ *                 ge_match_get's *found (and the message) carry the EXACT number of qualifying pairs, so the caller can raise
+ *                 the threshold or the cap.  Exactly max_pairs qualifying pairs is not an overflow.
+ *   groups        the connected components of the graph those pairs form over the indexed rows.  label[p] = the smallest
+ *                 original row id in the component of indexed position p; a row without a pair labels itself.
+ *   summary       pairs; components (rows without a pair included); groups = components of at least two rows; grouped_rows =
+ *                 rows inside those; largest = rows of the largest component.  Integer arithmetic throughout.
+ *   consequences  the bytes of a[], b[], score[], label[] and the summary are a function of the input alone: not of the grid,
+ *                 the order in which workgroups arrive (it decides scratch slots only; a radix sort by (a, b) follows), the
+ *                 stream, or an earlier run on the handle.  There are no floating-point atomics.  The index is a pure read of
+ *                 a trainer handle.
+ * Limits, checked on the host before any device work (GE_ERR_ARG without a GPU): the limits of ge_nn_create on rows, dim,
+ * subset and metric; a finite threshold; 1 <= max_pairs <= 2^28; no null mandatory argument.  Non-finite input rows: GE_ERR_ARG
+ * ("non-finite input").  No device: GE_ERR_HIP.  A defect inside the components kernels ends as GE_ERR_STATE, never as a kernel
+ * that does not return: every loop there is bounded by n.
+ * Device memory: the prepared table (n * D4 * 4 bytes, D4 = dim rounded up to 4) and 4 n bytes of row ids until
+ * ge_match_destroy; while a run is under way 12 bytes per slot for min(max_pairs, n (n - 1) / 2) slots, then 20 bytes per pair
+ * found and the sort's scratch, and 12 n bytes for the components.  The host keeps 12 bytes per pair and 4 n bytes of labels.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct ge_match ge_match;
+typedef struct {
+    int32_t metric;          /* GE_NN_COSINE or GE_NN_DOT */
+    int32_t device;          /* HIP device ordinal */
+    void   *stream;          /* hipStream_t or NULL */
+} ge_match_cfg;
+typedef struct { int64_t pairs, components, groups, grouped_rows, largest; } ge_match_summary;
+void      ge_match_cfg_default(ge_match_cfg *cfg);        /* cosine, device 0, null stream */
+int32_t   ge_match_cfg_size(void);
+int32_t   ge_match_summary_size(void);
+/* rows, subset: as ge_nn_create.  The index lives on the device until ge_match_destroy. */
+ge_status ge_match_create(const float *rows, int64_t n_rows, int32_t dim, const int32_t *subset, int64_t n_subset,
+                          const ge_match_cfg *cfg, ge_match **out);
+/* The same on the vectors a trainer handle holds; runs on the handle's device (cfg->device is ignored), writes no trainer table. */
+ge_status ge_glove_match_create(ge_glove *h, const int32_t *subset, int64_t n_subset, const ge_match_cfg *cfg, ge_match **out);
+/* One join, sort and components pass.  The threshold and max_pairs are looked at first, then the handle. */
+ge_status ge_match_run(ge_match *p, float threshold, int64_t max_pairs);
+/* HOST views owned by the handle, valid until the next ge_match_run or ge_match_destroy: a, b, score: [summary.pairs];
+ * label: [*n_indexed], by position.  *found: the qualifying pairs of the last run (0 before the first).  Before the first run,
+ * after an overflow (summary.pairs = *found then, the other fields 0) and after a failed run the views are NULL.
+ * Any out pointer may be NULL. */
+ge_status ge_match_get(const ge_match *p, int64_t *n_indexed, int64_t *found, const int32_t **a, const int32_t **b, const float **score,
+                       const int32_t **label, ge_match_summary *summary);
+/* Device time, hipEvents around the kernels, in milliseconds (0 = none ran); copies are not counted.  prepare: at creation.
+ * Of the last run: join (k_match_join), sort (the radix sort and the ids), components (hook, compress, summary).
+ * Any out pointer may be NULL. */
+ge_status ge_match_last_kernel_ms(const ge_match *p, float *prepare_ms, float *join_ms, float *sort_ms, float *components_ms);
+void      ge_match_destroy(ge_match *p);
+
 /* ------------------------------------------------------------------------------------------ */
-const char *ge_last_error(void);     /* message of the calling thread's last failed call */
+const char *ge_last_error(void);    /* message of the calling thread's last failed call */
 const char *ge_version(void);
 /* sizeof(ge_glove_cfg) as the LIBRARY was compiled: a host built against another header revision must refuse to
  * run instead of letting ge_glove_cfg_default write past its struct. */

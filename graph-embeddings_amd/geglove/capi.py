@@ -60,6 +60,8 @@ SYMBOLS = (
     "ge_classify_destroy",
     "ge_match_cfg_default", "ge_match_cfg_size", "ge_match_summary_size", "ge_match_create", "ge_glove_match_create", "ge_match_run",
     "ge_match_get", "ge_match_last_kernel_ms", "ge_match_destroy",
+    "ge_align_cfg_default", "ge_align_cfg_size", "ge_align_summary_size", "ge_align_create", "ge_glove_align_create", "ge_align_run",
+    "ge_align_get", "ge_align_last_kernel_ms", "ge_align_destroy",
 )
 GE_FOLD_FOCUS, GE_FOLD_CONTEXT = 0, 1
 FOLD_SIDES = {"focus": GE_FOLD_FOCUS, "context": GE_FOLD_CONTEXT}
@@ -170,6 +172,15 @@ class MatchCfg(C.Structure):
 
 class MatchSummary(C.Structure):
     _fields_ = [("pairs", C.c_int64), ("components", C.c_int64), ("groups", C.c_int64), ("grouped_rows", C.c_int64), ("largest", C.c_int64)]
+
+
+class AlignCfg(C.Structure):
+    _fields_ = [("metric", C.c_int32), ("device", C.c_int32), ("stream", C.c_void_p)]
+
+
+class AlignSummary(C.Structure):
+    _fields_ = [("candidates", C.c_int64), ("assigned", C.c_int64), ("mutual", C.c_int64), ("sources_with_candidates", C.c_int64),
+                ("targets_with_candidates", C.c_int64), ("ambiguous_sources", C.c_int64)]
 
 
 class SynthCfg(C.Structure):
@@ -306,6 +317,7 @@ def lib():
     _declare_ivf(L)
     _declare_classify(L)
     _declare_match(L)
+    _declare_align(L)
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int:      # default restype -> ge_status
@@ -1431,6 +1443,107 @@ class Classifier:
     def close(self):
         if self._h:
             lib().ge_classify_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _declare_align(L):
+    """The alignment section of include/geglove.h."""
+    vp, i32p, f32p, i64p, u8p = C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_int64), C.POINTER(C.c_uint8)
+    L.ge_align_cfg_default.argtypes = [C.POINTER(AlignCfg)]; L.ge_align_cfg_default.restype = None
+    L.ge_align_cfg_size.argtypes = []; L.ge_align_cfg_size.restype = C.c_int32
+    L.ge_align_summary_size.argtypes = []; L.ge_align_summary_size.restype = C.c_int32
+    if L.ge_align_cfg_size() != C.sizeof(AlignCfg) or L.ge_align_summary_size() != C.sizeof(AlignSummary):
+        raise ImportError("libgeglove.so was built from another revision of include/geglove.h (ge_align_cfg is %d bytes there, %d here; "
+                          "ge_align_summary %d there, %d here): rebuild with `make -C graph-embeddings_amd/csrc`"
+                          % (L.ge_align_cfg_size(), C.sizeof(AlignCfg), L.ge_align_summary_size(), C.sizeof(AlignSummary)))
+    L.ge_align_create.argtypes = [f32p, C.c_int64, C.c_int32, i32p, C.c_int64, i32p, C.c_int64, C.POINTER(AlignCfg), C.POINTER(vp)]
+    L.ge_glove_align_create.argtypes = [vp, i32p, C.c_int64, i32p, C.c_int64, C.POINTER(AlignCfg), C.POINTER(vp)]
+    L.ge_align_run.argtypes = [vp, C.c_float, C.c_int64]
+    L.ge_align_get.argtypes = [vp, i64p, i64p, i64p, C.POINTER(i32p), C.POINTER(i32p), C.POINTER(f32p), C.POINTER(i32p), C.POINTER(f32p),
+                               C.POINTER(u8p), C.POINTER(i32p), C.POINTER(AlignSummary)]
+    L.ge_align_last_kernel_ms.argtypes = [vp, f32p, f32p, f32p, f32p, i32p]
+    L.ge_align_destroy.argtypes = [vp]; L.ge_align_destroy.restype = None
+
+
+class Alignment:
+    """A ge_align index: Alignment.from_rows(rows, source, target) / Alignment.from_glove(handle, source, target), then
+    run(threshold, max_pairs) -> (int32[m] a, int32[m] b, float32[m] score, int32[nA] target_of, float32[nA] target_score,
+    uint8[nA] flags, int32[nB] source_of, summary dict): every (source, target) pair of original row ids whose score reaches the
+    threshold, in ascending (a, b), and the one-to-one assignment a greedy walk in descending score makes of them (flags: bit 0 =
+    assigned, bit 1 = mutual).  More than max_pairs candidates: GeError with status GE_ERR_OVERFLOW; found() gives the number."""
+
+    def __init__(self, handle, stream=None):
+        self._h = handle
+        self._stream = stream
+
+    @staticmethod
+    def _cfg(metric, device, stream):
+        cfg = AlignCfg(); lib().ge_align_cfg_default(C.byref(cfg))
+        cfg.metric, cfg.device, cfg.stream = NN_METRICS.get(metric, metric), device, stream
+        return cfg
+
+    @staticmethod
+    def _set(ids):
+        import numpy as np
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        return ids, ids.ctypes.data_as(C.POINTER(C.c_int32)), ids.size
+
+    @classmethod
+    def from_rows(cls, rows, source, target, metric="cosine", device=0, stream=None):
+        import numpy as np
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        (_s, sp, ns), (_t, tp, nt) = cls._set(source), cls._set(target)
+        h = C.c_void_p()
+        check(lib().ge_align_create(rows.ctypes.data_as(C.POINTER(C.c_float)), rows.shape[0], rows.shape[1], sp, ns, tp, nt,
+                                    C.byref(cls._cfg(metric, device, stream)), C.byref(h)))
+        return cls(h, stream)
+
+    @classmethod
+    def from_glove(cls, glove_handle, source, target, metric="cosine", stream=None):
+        (_s, sp, ns), (_t, tp, nt) = cls._set(source), cls._set(target)
+        h = C.c_void_p()
+        check(lib().ge_glove_align_create(glove_handle, sp, ns, tp, nt, C.byref(cls._cfg(metric, 0, stream)), C.byref(h)))
+        return cls(h, stream)
+
+    def found(self):
+        """The candidates of the last run, also after an overflow."""
+        n = C.c_int64()
+        check(lib().ge_align_get(self._h, None, None, C.byref(n), None, None, None, None, None, None, None, None))
+        return n.value
+
+    def run(self, threshold, max_pairs=1 << 24):
+        import numpy as np
+        check(lib().ge_align_run(self._h, threshold, max_pairs))
+        i32p, f32p, u8p = C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_uint8)
+        na, nb, summary = C.c_int64(), C.c_int64(), AlignSummary()
+        a, b, score, target_of, target_score, flags, source_of = i32p(), i32p(), f32p(), i32p(), f32p(), u8p(), i32p()
+        check(lib().ge_align_get(self._h, C.byref(na), C.byref(nb), None, C.byref(a), C.byref(b), C.byref(score), C.byref(target_of),
+                                 C.byref(target_score), C.byref(flags), C.byref(source_of), C.byref(summary)))
+        m = summary.candidates
+
+        def copy(ptr, count, dtype):          # the views are the handle's: copy them out
+            return np.ctypeslib.as_array(ptr, shape=(count,)).astype(dtype, copy=True) if count else np.empty(0, dtype)
+
+        return (copy(a, m, np.int32), copy(b, m, np.int32), copy(score, m, np.float32), copy(target_of, na.value, np.int32),
+                copy(target_score, na.value, np.float32), copy(flags, na.value, np.uint8), copy(source_of, nb.value, np.int32),
+                {k: getattr(summary, k) for k, _ in AlignSummary._fields_})
+
+    def kernel_ms(self):
+        """(prepare, join, sort, assign) device milliseconds and the assignment rounds: of creation, and of the last run"""
+        v = [C.c_float() for _ in range(4)]
+        rounds = C.c_int32()
+        check(lib().ge_align_last_kernel_ms(self._h, *[C.byref(x) for x in v], C.byref(rounds)))
+        return tuple(x.value for x in v) + (rounds.value,)
+
+    def close(self):
+        if self._h:
+            lib().ge_align_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -294,7 +294,13 @@ struct Configuration {
              // and the groups those pairs connect in <name>.entities.tsv; cosine | dot; at most `match_max_pairs` pairs (2^24);
              // an absent key is off; match is NaN for a value that is no finite number, match_max_pairs -1 for one that is no
              // integer >= 0, -2 = not set
-             bool has_match = false; double match = 0; std::string match_metric; long long match_max_pairs = -2; } device;
+             bool has_match = false; double match = 0; std::string match_metric; long long match_max_pairs = -2;
+             // align: T -- after the vectors, join the kept vertices whose key begins with `align_source` with those whose key begins
+             // with `align_target`, keep the pairs whose score reaches T and assign them one to one, best first (ge_align_*), in
+             // <name>.alignment.tsv; cosine | dot; at most `align_max_pairs` candidates (2^24); the same conventions as `match`;
+             // has_align_source / has_align_target: the key is there (its value may be empty, which is refused)
+             bool has_align = false; double align = 0; bool has_align_source = false, has_align_target = false;
+             std::string align_source, align_target, align_metric; long long align_max_pairs = -2; } device;
     std::vector<std::string> ignored_keys;     // legacy keys of the shipped YAMLs that the bean does not know
 
     int getThreads() const {       // Configuration.java:71-73
@@ -318,6 +324,9 @@ struct Configuration {
     bool matching() const { return device.has_match; }
     std::string matchMetric() const { return device.match_metric.empty() ? "cosine" : device.match_metric; }
     long long matchMaxPairs() const { return device.match_max_pairs == -2 ? (1LL << 24) : device.match_max_pairs; }
+    bool aligning() const { return device.has_align; }
+    std::string alignMetric() const { return device.align_metric.empty() ? "cosine" : device.align_metric; }
+    long long alignMaxPairs() const { return device.align_max_pairs == -2 ? (1LL << 24) : device.align_max_pairs; }
     // the whole scalar as a number, else NaN (which fails every range check)
     static double whole_fraction(const YNode &n) {
         const std::string &t = n.scalar;
@@ -445,6 +454,11 @@ struct Configuration {
                     else if (q.first == "match") { c.device.has_match = true; c.device.match = whole_fraction(q.second); }
                     else if (q.first == "match_metric") c.device.match_metric = q.second.kind == YNode::Scalar && !q.second.scalar.empty() ? q.second.scalar : "?";
                     else if (q.first == "match_max_pairs") c.device.match_max_pairs = whole_number(q.second);
+                    else if (q.first == "align") { c.device.has_align = true; c.device.align = whole_fraction(q.second); }
+                    else if (q.first == "align_source") { c.device.has_align_source = true; c.device.align_source = q.second.kind == YNode::Scalar ? q.second.scalar : ""; }
+                    else if (q.first == "align_target") { c.device.has_align_target = true; c.device.align_target = q.second.kind == YNode::Scalar ? q.second.scalar : ""; }
+                    else if (q.first == "align_metric") c.device.align_metric = q.second.kind == YNode::Scalar && !q.second.scalar.empty() ? q.second.scalar : "?";
+                    else if (q.first == "align_max_pairs") c.device.align_max_pairs = whole_number(q.second);
                     else if (q.first == "exchange") c.device.exchange = q.second.scalar;        // overlap | sync
                     else if (q.first == "transport") c.device.transport = q.second.scalar;      // auto | rccl | host
                     else if (q.first == "wire") c.device.wire = q.second.scalar;                // bf16 | f32
@@ -537,6 +551,20 @@ struct Configuration {
         if (c.matching() && c.matchMetric() != "cosine" && c.matchMetric() != "dot") throw InvalidConfigurationException("Invalid device.match_metric, choose one of: cosine, dot");
         if (c.matching() && (c.matchMaxPairs() < 1 || c.matchMaxPairs() > (1LL << 28)))
             throw InvalidConfigurationException("Invalid device.match_max_pairs, choose a number from 1 to 268435456");
+        if (!c.aligning() && (c.device.has_align_source || c.device.has_align_target || !c.device.align_metric.empty() || c.device.align_max_pairs != -2))
+            throw InvalidConfigurationException("device.align_source, device.align_target, device.align_metric and device.align_max_pairs need device.align");
+        if (c.aligning()) {
+            const std::string &src = c.device.align_source, &tgt = c.device.align_target;
+            if (!(std::fabs(c.device.align) <= (double)std::numeric_limits<float>::max()))     // the library takes it as fp32
+                throw InvalidConfigurationException("Invalid device.align, choose a finite score threshold");
+            if (src.empty() || tgt.empty())
+                throw InvalidConfigurationException("device.align needs device.align_source and device.align_target, the key prefixes of the two sets");
+            if (src.compare(0, tgt.size(), tgt) == 0 || tgt.compare(0, src.size(), src) == 0)
+                throw InvalidConfigurationException("device.align_source and device.align_target overlap: one prefix begins with the other");
+            if (c.alignMetric() != "cosine" && c.alignMetric() != "dot") throw InvalidConfigurationException("Invalid device.align_metric, choose one of: cosine, dot");
+            if (c.alignMaxPairs() < 1 || c.alignMaxPairs() > (1LL << 28))
+                throw InvalidConfigurationException("Invalid device.align_max_pairs, choose a number from 1 to 268435456");
+        }
     }
 
     static std::string similarity_to_string(const std::map<std::string, std::string> &m) {     // SimilarityGroup.toString
@@ -594,6 +622,8 @@ struct Configuration {
                                        ", " + device.classify_normalize + ", at most " + std::to_string(device.classify_iterations) + " iterations)");
         if (matching()) L.push_back("Match: pairs scoring at least " + java_number(device.match, false) + " (" + matchMetric() + ", at most " +
                                     std::to_string(matchMaxPairs()) + " pairs)");
+        if (aligning()) L.push_back("Align: " + device.align_source + " to " + device.align_target + ", pairs scoring at least " + java_number(device.align, false) +
+                                    " (" + alignMetric() + ", at most " + std::to_string(alignMaxPairs()) + " pairs)");
         return L;
     }
 };
@@ -1924,6 +1954,78 @@ inline std::string writeMatches(const Configuration &config, const Optimum &opti
     return "matched " + std::to_string(pairs) + " " + config.matchMetric() + " pairs scoring at least " + java_number(config.device.match, false) + " among " +
            std::to_string(kept) + " vertices: " + std::to_string(summary.groups) + " entities of " + std::to_string(summary.grouped_rows) + " vertices, the largest of " +
            std::to_string(summary.largest) + "; wrote " + outputFolder + "/" + file + " and " + outputFolder + "/" + groups;
+}
+
+// `device: { align: T, align_source: P, align_target: Q }`: the kept vertices (the ones writeNeighbors lists) whose key, as the dict
+// file writes it, begins with P are the sources, those whose key begins with Q the targets (the configuration refuses prefixes that
+// overlap); every (source, target) pair whose score reaches T is a candidate, and the candidates are assigned one to one, best
+// first (ge_align_*), from the final result (after `device.pca: apply`), on device.id, once -- also after a multi-GPU run.
+// <fileName>.alignment.tsv carries the banner, then one line keySource<TAB>keyTarget<TAB>score<TAB>mutual per assigned pair in
+// ascending source id, the score in the number format of the vectors file, mutual 1 or 0.  An empty set is a run-time error that
+// names its prefix; more than `align_max_pairs` candidates is one that names the number found and the key to raise; no file is
+// written then.  Returns the line Main logs.
+inline std::string writeAlignment(const Configuration &config, const Optimum &optimum, const CoOccurrenceMatrix &m, const std::string &fileName,
+                                  const std::string &outputFolder) {
+    if (ge_align_cfg_size() != (int32_t)sizeof(ge_align_cfg) || ge_align_summary_size() != (int32_t)sizeof(ge_align_summary))
+        throw std::runtime_error("libgeglove.so and this host were built from different revisions of include/geglove.h; rebuild both");
+    const int V = m.vocabSize();
+    if (V < 1 || optimum.result.size() % (size_t)V != 0) throw std::runtime_error("align: the result is not a table of V rows");
+    const int D = (int)(optimum.result.size() / (size_t)V);
+    auto clean = [&](int vertex) {                                                  // a key as the dict file writes it
+        std::string out;
+        for (char ch : m.getKey(vertex)) if (ch != '\n' && ch != '\r' && ch != '\t') out.push_back(ch);
+        return out;
+    };
+    const std::string &src = config.device.align_source, &tgt = config.device.align_target;
+    std::vector<int32_t> source, target;                                            // ascending: keptVertices ascends
+    for (int v : keptVertices(config, m)) {
+        const std::string key = clean(v);
+        if (key.compare(0, src.size(), src) == 0) source.push_back(v);
+        else if (key.compare(0, tgt.size(), tgt) == 0) target.push_back(v);
+    }
+    if (source.empty()) throw std::runtime_error("align: no written vertex has a key that begins with device.align_source: " + src);
+    if (target.empty()) throw std::runtime_error("align: no written vertex has a key that begins with device.align_target: " + tgt);
+    const std::vector<float> rows(optimum.result.begin(), optimum.result.end());    // widened fp32 values: exact
+    ge_align_cfg cfg;
+    ge_align_cfg_default(&cfg);
+    cfg.metric = config.alignMetric() == "dot" ? GE_NN_DOT : GE_NN_COSINE;
+    cfg.device = config.device.id;
+    struct Del { void operator()(ge_align *p) const { ge_align_destroy(p); } };
+    ge_align *raw = nullptr;
+    check(ge_align_create(rows.data(), V, D, source.data(), (int64_t)source.size(), target.data(), (int64_t)target.size(), &cfg, &raw));
+    std::unique_ptr<ge_align, Del> align(raw);
+    const ge_status st = ge_align_run(raw, (float)config.device.align, (int64_t)config.alignMaxPairs());
+    if (st == GE_ERR_OVERFLOW) {
+        int64_t found = 0;
+        check(ge_align_get(raw, nullptr, nullptr, &found, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+        throw std::runtime_error("align: " + std::to_string(found) + " pairs reach device.align: " + java_number(config.device.align, false) +
+                                 ", more than device.align_max_pairs: " + std::to_string(config.alignMaxPairs()) +
+                                 "; raise device.align or device.align_max_pairs");
+    }
+    check(st);
+    const int32_t *target_of = nullptr;
+    const float *target_score = nullptr;
+    const uint8_t *flags = nullptr;
+    ge_align_summary summary{};
+    check(ge_align_get(raw, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &target_of, &target_score, &flags, nullptr, &summary));
+    std::filesystem::create_directories(outputFolder);
+    const std::string file = fileName + ".alignment.tsv";
+    std::ofstream out(outputFolder + "/" + file);
+    if (!out) throw std::runtime_error("cannot open " + file + " in " + outputFolder);
+    for (auto &l : config.banner()) out << "# " << l << "\n";
+    std::string line;
+    char num[40];
+    for (size_t k = 0; k < source.size(); ++k) {
+        if (!(flags[k] & 1)) continue;
+        line = clean(source[k]);
+        line += '\t'; line += clean(target_of[k]);
+        line += '\t'; line.append(num, (size_t)java_format_11_6E_to((double)target_score[k], num));
+        line += '\t'; line += (flags[k] & 2) ? '1' : '0';
+        line += '\n';
+        out.write(line.data(), (std::streamsize)line.size());
+    }
+    return "aligned " + std::to_string(summary.assigned) + " of " + std::to_string(source.size()) + " " + src + " with " + std::to_string(target.size()) + " " + tgt +
+           " (" + std::to_string(summary.candidates) + " candidates, " + std::to_string(summary.mutual) + " mutual); wrote " + outputFolder + "/" + file;
 }
 
 // `device: { holdout: F }`: <fileName>.holdout.tsv carries the banner, then one line per epoch: the iteration as ge_glove_epoch

@@ -4,7 +4,8 @@
 // <name>.rank.tsv with `device: { rank: Q }`, <name>.clusters.tsv with `device: { clusters: K }`,
 // <name>.links.tsv with `device: { predict: K }`, <name>.foldin.tsv with `device: { foldin: F }`,
 // <name>.classes.tsv with `device: { classify: labels.tsv }`,
-// <name>.matches.tsv and <name>.entities.tsv with `device: { match: T }`).
+// <name>.matches.tsv and <name>.entities.tsv with `device: { match: T }`,
+// <name>.alignment.tsv with `device: { align: T, align_source: P, align_target: Q }`).
 #include <ctime>
 #include "ge_host.hpp"
 
@@ -140,6 +141,7 @@ static void runProgram(const Configuration &given) {                        // J
         log_info("Classify", done);
     }
     if (config.matching()) log_info("Match", writeMatches(config, optimum, bca, outFileName, "out"));
+    if (config.aligning()) log_info("Align", writeAlignment(config, optimum, bca, outFileName, "out"));
     g_optimizer = nullptr;
 }
 

@@ -1285,6 +1285,83 @@ ge_status ge_match_get(const ge_match *p, int64_t *n_indexed, int64_t *found, co
 ge_status ge_match_last_kernel_ms(const ge_match *p, float *prepare_ms, float *join_ms, float *sort_ms, float *components_ms);
 void      ge_match_destroy(ge_match *p);
 
+/* ------------------------------------------------------------------------------------------
+ * Alignment: which vertex of set A is which vertex of set B, each used at most once?  A rectangular join source x target above
+ * a threshold, then the one-to-one assignment of a greedy walk over the candidates in descending score, on one device.  The
+ * reference compares literals at ingest (CompareJob); on the vectors it has no counterpart, so these are product semantics.
+ *   indexed rows  one table, taken exactly as ge_match_create takes it (host rows [n_rows][dim], or the vectors of a trainer
+ *                 handle: ge_glove_align_create), and two mandatory subsets of original row ids: source (nA >= 1 ids) and
+ *                 target (nB >= 1 ids), each strictly ascending and inside [0, n_rows), and disjoint from each other.  Source
+ *                 position p is the p-th source id, target position q the q-th target id.  Prepared row as ge_nn_*: COSINE:
+ *                 n = sqrt(sum_d x_d^2), accumulated in fp64 in ascending d; xh_d = (float)((double)x_d / n), rounded once; a
+ *                 zero row stays zero.  DOT: xh = x.
+ *   score         s(a, b) = sum_d xh_a[d] * xh_b[d], an fp32 fmaf chain from +0 in ascending d (k_align_join on the fp32 matrix
+ *                 cores): the bits ge_nn_* and ge_match_* return for that pair.  A sum that ends as NaN counts as -inf.
+ *   candidates    ge_align_run(p, threshold, max_pairs): all (a in source, b in target) with s(a, b) >= threshold as fp32
+ *                 compares them, listed once each in ascending (a, b) (ORIGINAL row ids) with the score bits.
+ *   overflow      more than max_pairs candidates: GE_ERR_OVERFLOW.  The handle then holds nothing; ge_align_get's *found (and
+ *                 the message) carry the EXACT number of candidates.  Exactly max_pairs candidates is not an overflow.
+ *   order         candidate (a, b, s) comes before (a', b', s') if s > s' as fp32 compares them (so -0 equals +0), or the scores
+ *                 compare equal and a < a', or the scores compare equal, a = a' and b < b'.  A strict total order.
+ *   assignment    walk the candidates in that order and accept (a, b) if neither a nor b has been accepted before.  The
+ *                 accepted pairs are the alignment: no source and no target occurs twice, and no candidate is left with both
+ *                 ends free.  (The device computes the same set in parallel rounds: every free vertex points at the first
+ *                 candidate of its own that is still free, and a source and a target that point at each other are paired; under
+ *                 a strict total order the best remaining candidate is always such a pair.)
+ *   mutual        an accepted pair is mutual when b is the first candidate of a in the order and a is the first candidate of b:
+ *                 the mutual-nearest-neighbour criterion.  Every such pair is accepted.
+ *   outputs       a[], b[], score[]: the candidates.  By source position p: target_of[p] = the original id of the assigned
+ *                 target or -1; target_score[p] = that pair's score bits, +0 where there is none; flags[p]: bit 0 = assigned,
+ *                 bit 1 = mutual.  By target position q: source_of[q] = an original id or -1.
+ *   summary       candidates; assigned; mutual; sources_with_candidates; targets_with_candidates; ambiguous_sources = sources
+ *                 with at least two candidates.  Integer arithmetic throughout.
+ *   consequences  the bytes of every output are a function of the rows, the two subsets, the metric, the threshold and max_pairs
+ *                 (through the overflow rule only): not of the grid, the order in which workgroups arrive (it decides scratch
+ *                 slots only; radix sorts by key follow), the stream, or an earlier run on the handle.  There are no
+ *                 floating-point atomics.  The index is a pure read of a trainer handle.
+ * Limits, checked on the host before any device work (GE_ERR_ARG without a GPU): the limits of ge_match_create on rows, dim
+ * (1..1024), table size and metric; both subsets present, each strictly ascending and in range; "the source and target sets share
+ * row %d" for a shared id; a finite threshold and 1 <= max_pairs <= 2^28 (looked at before the handle); no null mandatory
+ * argument.  Non-finite input rows: GE_ERR_ARG ("non-finite input").  No device: GE_ERR_HIP.  A defect inside the assignment
+ * kernels ends as GE_ERR_STATE, never as a kernel that does not return: a cursor stays inside its list, and one assigning round
+ * more than min(nA, nB) stops the run.
+ * Device memory: the two prepared tables ((nA + nB) * D4 * 4 bytes, D4 = dim rounded up to 4) and 4 (nA + nB) bytes of row ids
+ * until ge_align_destroy; while a run is under way 12 bytes per slot for min(max_pairs, nA * nB) slots, then 56 bytes per
+ * candidate and the sorts' scratch, and 29 nA + 20 nB bytes (the list starts included) for the assignment.  The
+ * host keeps 12 bytes per candidate, 9 nA and 4 nB bytes.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct ge_align ge_align;
+typedef struct {
+    int32_t metric;          /* GE_NN_COSINE or GE_NN_DOT */
+    int32_t device;          /* HIP device ordinal */
+    void   *stream;          /* hipStream_t or NULL */
+} ge_align_cfg;
+typedef struct { int64_t candidates, assigned, mutual, sources_with_candidates, targets_with_candidates, ambiguous_sources; } ge_align_summary;
+void      ge_align_cfg_default(ge_align_cfg *cfg);        /* cosine, device 0, null stream */
+int32_t   ge_align_cfg_size(void);
+int32_t   ge_align_summary_size(void);
+/* rows: as ge_match_create; source, target: the two sets.  The index lives on the device until ge_align_destroy. */
+ge_status ge_align_create(const float *rows, int64_t n_rows, int32_t dim, const int32_t *source, int64_t n_source,
+                          const int32_t *target, int64_t n_target, const ge_align_cfg *cfg, ge_align **out);
+/* The same on the vectors a trainer handle holds; runs on the handle's device (cfg->device is ignored), writes no trainer table. */
+ge_status ge_glove_align_create(ge_glove *h, const int32_t *source, int64_t n_source, const int32_t *target, int64_t n_target,
+                                const ge_align_cfg *cfg, ge_align **out);
+/* One join, the sorts and the assignment.  The threshold and max_pairs are looked at first, then the handle. */
+ge_status ge_align_run(ge_align *p, float threshold, int64_t max_pairs);
+/* HOST views owned by the handle, valid until the next ge_align_run or ge_align_destroy: a, b, score: [summary.candidates];
+ * target_of, target_score, flags: [*n_source], by source position; source_of: [*n_target], by target position.  *found: the
+ * candidates of the last run (0 before the first).  Before the first run, after an overflow (summary.candidates = *found then,
+ * the other fields 0) and after a failed run the views are NULL.  Any out pointer may be NULL. */
+ge_status ge_align_get(const ge_align *p, int64_t *n_source, int64_t *n_target, int64_t *found, const int32_t **a, const int32_t **b,
+                       const float **score, const int32_t **target_of, const float **target_score, const uint8_t **flags,
+                       const int32_t **source_of, ge_align_summary *summary);
+/* Device time, hipEvents around the kernels, in milliseconds (0 = none ran); copies are not counted.  prepare: at creation.
+ * Of the last run: join (k_align_join), sort (the three radix sorts, the keys and the list starts), assign (the rounds, the
+ * host's looks at their counters included, the ids and the summary).  *rounds: the assignment rounds of the last run, a
+ * diagnostic.  Any out pointer may be NULL. */
+ge_status ge_align_last_kernel_ms(const ge_align *p, float *prepare_ms, float *join_ms, float *sort_ms, float *assign_ms, int32_t *rounds);
+void      ge_align_destroy(ge_align *p);
+
 /* ------------------------------------------------------------------------------------------ */
 const char *ge_last_error(void);    /* message of the calling thread's last failed call */
 const char *ge_version(void);
